@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- k-mers/s of the count hot path on synthetic reads.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default workload (N = 1) = BASELINE.json configs[2] at the largest scale whose table fits one MI355X next to the
@@ -9,9 +9,14 @@ resident read set ("human-scale": G-Mbp iid genome, 30x 150 bp reads with 0.5 % 
 device, k = 21, count, then validate the assembly = genome with 1e-4 substitutions).  The read set is cut into K
 equal batches; a "step" = one batch through the count hot path (hashSequences + processBuffers).  The timed region
 counts the K batches into ONE table that starts empty and ends with everything applied (kq_sync), inputs resident in
-HBM.  value = read k-mers / wall time.  The line also carries: `validate` (assembly lookup + QV), `configs1`
-(BASELINE configs[1], 1 M x 150 bp: steady state of several batches into one table and the empty-table figure that
-was round 1's headline), `lookup` and `union` (driver-timed, with their own roofline fractions), `cpu_baseline`.
+HBM.  value = read k-mers / wall time.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline does not need:
+`validate` (assembly lookup + QV), `configs1` (BASELINE configs[1], 1 M x 150 bp: steady state of several batches
+into one table and the empty-table figure that was round 1's headline), `lookup` and `union` (driver-timed, with their
+own roofline fractions), `third_scale`, `cpu_baseline`, and for --workload cfg1 the per-stage times (`stage_ms`).
+--dump-outputs DIR writes, after the timed steps, what the last step left in the table (summary counters, coverage
+histogram, and the entries of a fixed, seeded sample of the read k-mers) as DIR/<name>.npy (float64), one GPU only.
 
 N > 1 runs the SAME read set sharded (BASELINE configs[3], strong scaling): every rank generates 1/N of each batch,
 routes the k-mer records to the rank that owns their hash-bucket range with an RCCL all-to-all (kreeq_amd/dist.py),
@@ -46,6 +51,9 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s
 TABLE_MARGIN = 1.04          # table capacity hint over the expected distinct k-mers (the table is sized hint / 0.7 slots)
 TABLE_LOAD = 0.8             # load factor the human workload's table is sized for: expected distinct k-mers / slots (0.67 -> 0.8: -3 % at 3 Gbp; 0.85 another -4 %, but a region then overflows at 7 sigma)
 CPU_SAMPLE_READS = 5_000_000 # reads of the cpu_baseline sample
+DUMP_READS = 2048            # --dump-outputs: reads of the first batch whose k-mers are looked up in the final table
+DUMP_KEYS = 1 << 18          # --dump-outputs: at most this many distinct keys of them (~25 MB of .npy)
+DUMP_SEED = 7
 
 
 def qv(missing, total, k):
@@ -85,6 +93,9 @@ def main():
     ap.add_argument("-k", type=int, default=K, help="k-mer length (default 21 = BASELINE.json's metric)")
     ap.add_argument("--read-len", type=int, default=READ_LEN)
     ap.add_argument("--sharded", action="store_true", help="cfg1 with one GPU: still run the N>1 code path (owner split -> insert)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: validate, cpu_baseline, "
+                    "the configs1 / lookup / union / third_scale objects, cfg1 stage times")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (one GPU)")
     args = ap.parse_args()
 
     # stdout carries ONE line, the JSON: native libraries that print to file descriptor 1 (RCCL's version banner at
@@ -103,6 +114,8 @@ def main():
         if world == 1 and args.gpus > 1:
             sys.exit("--gpus N>1 must be launched with torch.distributed.run (one rank per GPU)")
         args.gpus = world
+    if args.dump_outputs and world > 1:
+        sys.exit("--dump-outputs needs one GPU: a rank's table holds only its own buckets")
     # rehearsal of the N > 1 path on ONE GPU (never the measured configuration): KQ_BENCH_ONE_GPU=1 puts every rank on
     # cuda:0 and KQ_BENCH_BACKEND=gloo replaces RCCL, which refuses two ranks on one device
     backend = os.environ.get("KQ_BENCH_BACKEND", "nccl")
@@ -173,16 +186,20 @@ def run_human(args, dev, world=1, rank=0):
     stream = torch.cuda.Stream(dev)
     torch.cuda.set_stream(stream)
     genome = synth.genome_dev(G, dev, seed=1)
+    # the assembly is made and kept resident in a plain run too: the map-range and arena plan below is sized from the free
+    # HBM next to it, so the timed configuration is the same with and without --full
     asm_codes, n_sub = synth.mutate_dev(genome, ASM_ERR, seed=3)
     assembly = synth.ascii_dev(asm_codes)
     del asm_codes
     gen = torch.Generator(device=dev)
     gen.manual_seed(2 + 1000 * rank)                  # every rank draws its own 1/world of each batch from the same genome
-    batches, cpu_sample = [], None
+    batches, cpu_sample, dump_reads = [], None, None
     for i in range(steps):
         t = synth.reads_dev(genome, batch_reads // world, L, gen, err=ERR)
-        if i == 0 and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if i == 0 and rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             cpu_sample = t[:min(batch_reads, CPU_SAMPLE_READS) * (L + 1) - 1].cpu().numpy()
+        if i == 0 and args.dump_outputs:
+            dump_reads = sample_reads(t, batch_reads // world, L)
         if packed:
             codes, inv = synth.pack_dev(t)
             batches.append((codes, inv, t.numel()))
@@ -287,6 +304,7 @@ def run_human(args, dev, world=1, rank=0):
     dt = dev_ms = t_val = 0.0
     alt_kernels = [int(x) for x in args.alt_kernels.split(",") if x != ""]
     summ = {"total": 0, "unique": 0, "distinct": 0, "edges": 0}
+    hist = {}
     c = [0, 0, 0]
     table_passes, passes_before = [], db.info()["table_passes"]        # (the warm-up's pass is not the job's)
     info = None
@@ -314,21 +332,25 @@ def run_human(args, dev, world=1, rank=0):
             summ[f] += s_r[f]
         table_passes.append(info["table_passes"] - passes_before)
         passes_before = info["table_passes"]
-        # validate: the assembly's k-mers against the table (DBG::validateSequences); N > 1: own buckets + all-reduce
-        barrier()
-        tv = time.perf_counter()
-        if counter is not None:
-            c_r = counter.validate(assembly).tolist()
-        else:
-            ctr = torch.zeros(3, dtype=torch.int64, device=dev)
-            if by_bucket:                # the window answers for the k-mers of its buckets only
-                db.lookup_sequence_dev(assembly.data_ptr(), assembly.numel(), ctr.data_ptr())
+        if args.dump_outputs:
+            for cov, cnt in db.summary(with_hist=True)["hist"].items():
+                hist[cov] = hist.get(cov, 0) + cnt
+        if args.full:
+            # validate: the assembly's k-mers against the table (DBG::validateSequences); N > 1: own buckets + all-reduce
+            barrier()
+            tv = time.perf_counter()
+            if counter is not None:
+                c_r = counter.validate(assembly).tolist()
             else:
-                db.lookup_sequence_dev(assembly.data_ptr(), assembly.numel(), ctr.data_ptr(), map_lo=mlo, map_hi=mhi)
-            torch.cuda.synchronize(dev)
-            c_r = ctr.cpu().tolist()
-        t_val += time.perf_counter() - tv
-        c = [a + b for a, b in zip(c, c_r)]
+                ctr = torch.zeros(3, dtype=torch.int64, device=dev)
+                if by_bucket:                # the window answers for the k-mers of its buckets only
+                    db.lookup_sequence_dev(assembly.data_ptr(), assembly.numel(), ctr.data_ptr())
+                else:
+                    db.lookup_sequence_dev(assembly.data_ptr(), assembly.numel(), ctr.data_ptr(), map_lo=mlo, map_hi=mhi)
+                torch.cuda.synchronize(dev)
+                c_r = ctr.cpu().tolist()
+            t_val += time.perf_counter() - tv
+            c = [a + b for a, b in zip(c, c_r)]
         if r + 1 < n_ranges:
             db.clear()
     if world > 1:
@@ -337,9 +359,11 @@ def run_human(args, dev, world=1, rank=0):
         dt, dev_ms = float(tt[0]), float(tt[1])
     summ["missing"] = (4 ** k - summ["distinct"]) % (1 << 64)
     assert summ["total"] == n_kmers, (summ, kmers_per_step, steps)
-    assert c[1] == G - k + 1, c
+    assert not args.full or c[1] == G - k + 1, c
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, db, k, dump_reads, summ, hist, None if by_bucket else ranges[-1])
 
     value = n_kmers / dt
     ms_kernel = dev_ms / steps
@@ -360,7 +384,7 @@ def run_human(args, dev, world=1, rank=0):
                                f"({n_reads} reads, {ERR * 100:g} % substitutions, generated on the device"
                                + (", resident 2-bit packed" if packed else "") + f"), k={k}, count in {steps} batches"
                                + (f" x {n_ranges} map-range passes (every pass rescans all reads; wall time of all passes counted)" if n_ranges > 1 else "")
-                               + " + validate, "
+                               + (" + validate, " if args.full else ", ")
                                + (f"{world} GPUs, hash-bucket sharded with RCCL all-to-all" if world > 1 else "1 GPU"),
                    "genome_bp": G, "reads": n_reads, "reads_per_step": batch_reads, "error_rate": ERR, "table_capacity_kmers": hint,
                    "map_range_passes": n_ranges, "table_passes_per_range": table_passes, "table_passes_planned": passes_planned,
@@ -369,20 +393,21 @@ def run_human(args, dev, world=1, rank=0):
                    "count_path": args.path, "sharding": f"bucket x{world}" if sharded else "none"},
         "total_kmers_per_step": kmers_per_step, "distinct_kmers": summ["distinct"], "distinct_kmers_per_s": summ["distinct"] / dt,
         "summary": summ,
-        "validate": {"assembly_kmers": c[1], "substitutions": n_sub, "missing": c[0], "edge_missing": c[2], "ms": t_val * 1e3,
-                     "kmers_per_s": c[1] / t_val, "qv_merqury": qv(c[0], c[1], k), "qv_kreeq": qv(c[0] + c[2], c[1], k),
-                     "roofline_frac": c[1] * BYTES_PER_LOOKUP / t_val / 1e9 / HBM_PEAK_GBS},
         "roofline": {"bound": "hbm", "kernel": "count launch set per batch: k_p1_hist+k_p1_scatter+k_lv_hist+k_lv_scatter (x levels) per slice"
                                                + (f" and map range (x{n_ranges})" if n_ranges > 1 else "") + ", k_count_regions per table pass (+scans)",
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": traffic, "bytes_per_kmer": BYTES_PER_KMER, "kernel_ms": ms_kernel},
     }
+    if args.full:
+        out["validate"] = {"assembly_kmers": c[1], "substitutions": n_sub, "missing": c[0], "edge_missing": c[2], "ms": t_val * 1e3,
+                           "kmers_per_s": c[1] / t_val, "qv_merqury": qv(c[0], c[1], k), "qv_kreeq": qv(c[0] + c[2], c[1], k),
+                           "roofline_frac": c[1] * BYTES_PER_LOOKUP / t_val / 1e9 / HBM_PEAK_GBS}
     del db, batches, assembly
     torch.cuda.synchronize(dev)
     torch.cuda.empty_cache()
     if cpu_sample is not None:
         out["cpu_baseline"] = cpu_baseline(cpu_sample, k, L)
-    if not args.no_extras and world == 1 and not sharded:
+    if args.full and not args.no_extras and world == 1 and not sharded:
         out.update(extras_cfg1(dev, stream))
         if args.genome_mbp > 1000 and not args.no_third:
             out["third_scale"] = third_scale(dev, stream, args)
@@ -396,6 +421,7 @@ def third_scale(dev, stream, args):
 
     a = copy.copy(args)
     a.genome_mbp, a.no_extras, a.no_cpu_baseline, a.ranges, a.steps, a.warmup = 1000.0, True, True, 0, 20, 2
+    a.dump_outputs = None
     o = run_human(a, dev)
     return {"workload": o["config"]["workload"], "value": o["value"], "ms_per_step": o["ms_per_step"], "kmers_per_step": o["total_kmers_per_step"],
             "roofline_frac": o["roofline"]["frac"], "map_range_passes": o["config"]["map_range_passes"], "table_passes": o["config"]["table_passes"],
@@ -566,7 +592,7 @@ def run_cfg1(args, dev, world, rank, local_rank):
 
     # per-stage HIP-event times of one extra (untimed) step, for the roofline breakdown
     stages = None
-    if world == 1 and not args.sharded and args.path != "direct":
+    if args.full and world == 1 and not args.sharded and args.path != "direct":
         engine.db.set_option("profile", 1)
         step()
         stages = engine.db.profile()
@@ -577,6 +603,8 @@ def run_cfg1(args, dev, world, rank, local_rank):
     assert summ["total"] == kmers_per_rank * world or os.environ.get("KQ_BENCH_NOCHECK"), (summ, kmers_per_rank, world)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engine.db, K_, sample_reads(reads, args.reads, RL), summ, engine.histogram(), None)
     total_kmers = kmers_per_rank * world * args.steps
     value = total_kmers / dt
     achieved = kmers_per_rank * BYTES_PER_KMER / (kern_ms * 1e-3) / 1e9
@@ -593,9 +621,48 @@ def run_cfg1(args, dev, world, rank, local_rank):
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": None, "bytes_per_kmer": BYTES_PER_KMER, "kernel_ms": kern_ms, "stage_ms": stages},
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(reads_np, K_, RL)
     return out
+
+
+def sample_reads(t, n_reads, read_len):
+    """the fixed, seeded --dump-outputs sample of a read batch tensor (n_reads reads of read_len bases, '\\n' between
+    them) -> the sampled reads as one batch"""
+    import torch
+
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_reads, min(DUMP_READS, n_reads), replace=False))
+    rows = t.as_strided((n_reads, read_len), (read_len + 1, 1))[torch.from_numpy(pick).to(t.device)].cpu().numpy()
+    out = np.full((len(pick), read_len + 1), ord("\n"), dtype=np.uint8)
+    out[:, :-1] = rows
+    return out.tobytes()[:-1]
+
+
+def dump_outputs(out_dir, db, k, reads, summ, hist, map_range):
+    """What the timed path left in the table, as float64 .npy files: the summary counters, the coverage histogram, and the
+    entries of the distinct k-mers of `reads` (keys whose map key % 128 lies in map_range, the table's range; at most
+    DUMP_KEYS of them, a seeded choice), keys split in two 32-bit halves so that they stay exact."""
+    from oracle import oracle as O
+
+    keys = np.unique(O.emit_records(k, reads)[0])
+    if map_range is not None:
+        keys = keys[(keys % 128 >= map_range[0]) & (keys % 128 < map_range[1])]
+    if len(keys) > DUMP_KEYS:
+        keys = np.sort(np.random.default_rng(DUMP_SEED).choice(keys, DUMP_KEYS, replace=False))
+    ent = db.lookup_keys(keys)
+    arrays = {
+        "summary": np.array([summ[f] for f in ("total", "unique", "distinct", "missing", "edges")], dtype=np.float64),
+        "histogram": np.array(sorted(hist.items()), dtype=np.float64).reshape(-1, 2),
+        "sample_key": np.stack([ent["key"] >> np.uint64(32), ent["key"] & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64),
+        "sample_fw": ent["fw"].astype(np.float64),
+        "sample_bw": ent["bw"].astype(np.float64),
+        "sample_cov": ent["cov"].astype(np.float64),
+        "sample_hc": ent["hc"].astype(np.float64),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(reads_np, k=K, read_len=READ_LEN):

@@ -1,7 +1,7 @@
 """ctypes wrapper of the CPU oracle (oracle/kreeq_oracle.c).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
-leg -- never by kreeq_amd/ (the product).
+leg and --dump-outputs key sample -- never by kreeq_amd/ (the product).
 """
 import ctypes as C
 import os

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in "$@"; do
   if [ "$v" != x ]; then export $VAR=$v; else unset $VAR; fi
   rm -rf /tmp/p_stats
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -- python3 bench.py --genome-mbp ${GENOME_MBP:-3000} --steps 20 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p_stats -- python3 bench.py --full --genome-mbp ${GENOME_MBP:-3000} --steps 20 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$VAR=$v: %.2f ms/step  %.1f G/s  validate %.1f ms' % (d['ms_per_step'], d['value']/1e9, d['validate']['ms']))"
   python3 - <<PY
 import csv, glob

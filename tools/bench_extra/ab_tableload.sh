@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in "$@"; do
   rm -rf /tmp/p_stats
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-extras --table-load $v 2>/tmp/err.txt | python3 -c "
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p_stats -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-extras --table-load $v 2>$TMPDIR/err.txt | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('load $v: %.2f ms/step  %.1f G/s  passes %s  table %.1f GB  validate %.1f ms' % (d['ms_per_step'], d['value']/1e9, d['config']['table_passes_per_range'], d['config']['table_bytes']/1e9, d['validate']['ms']))" || tail -3 /tmp/err.txt
   python3 - <<PY
 import csv, glob

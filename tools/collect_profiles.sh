@@ -12,18 +12,18 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG
 mkdir -p $O
 if [ "$WHAT" = bench ]; then
-  timeout -k 10 700 python3 bench.py --genome-mbp $MBP --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+  timeout -k 10 700 python3 bench.py --full --genome-mbp $MBP --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
   echo "bench done"
   rm -rf /tmp/p_stats
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -- python3 bench.py --genome-mbp $MBP --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/stats_bench.json 2> $O/stats.err
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p_stats -- python3 bench.py --full --genome-mbp $MBP --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/stats_bench.json 2> $O/stats.err
   # the library's kernels only (the torch kernels that generate the reads have kilobyte-long names)
   S=$(find /tmp/p_stats -name "*kernel_stats.csv" | head -1)
   head -1 $S > $O/kernel_stats.csv
   grep -E "^\"(void )?k_|rocclr" $S >> $O/kernel_stats.csv
   echo "stats done"
-  timeout -k 10 300 python3 bench.py --workload cfg1 --steps 20 --warmup 3 --no-cpu-baseline > $O/cfg1_bench.json 2> $O/cfg1_bench.err
+  timeout -k 10 300 python3 bench.py --full --workload cfg1 --steps 20 --warmup 3 --no-cpu-baseline > $O/cfg1_bench.json 2> $O/cfg1_bench.err
   rm -rf /tmp/p_stats1
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats1 -- python3 bench.py --workload cfg1 --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2> $O/cfg1_stats.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p_stats1 -- python3 bench.py --full --workload cfg1 --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2> $O/cfg1_stats.err
   cp $(find /tmp/p_stats1 -name "*kernel_stats.csv" | head -1) $O/cfg1_kernel_stats.csv
 else
   C=FETCH_SIZE; [ "$WHAT" = write ] && C=WRITE_SIZE
