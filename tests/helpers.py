@@ -157,3 +157,120 @@ VCF_GOLDEN_DEVIATION = {
 def vcf_expected(lines):
     """test.50.tst's expectation with the one documented deviation applied"""
     return [VCF_GOLDEN_DEVIATION.get(l, l) for l in lines]
+
+
+# ---------------------------------------------------------------------------------- k-dependent inputs (test_*kmatrix*)
+# Keys pack a k-mer two bits per base, first base in the low bits (oracle/kreeq_oracle.c kqo_hash); the canonical key is
+# min(forward, reverse complement), and a palindrome (forward == reverse complement, even k only) counts as not forward.
+ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+def revcomp_keys(keys, k):
+    """reverse complement of packed keys (numpy uint64 array, any shape)"""
+    x = ~np.asarray(keys, dtype=np.uint64)
+    x = ((x >> np.uint64(2)) & np.uint64(0x3333333333333333)) | ((x & np.uint64(0x3333333333333333)) << np.uint64(2))
+    x = ((x >> np.uint64(4)) & np.uint64(0x0F0F0F0F0F0F0F0F)) | ((x & np.uint64(0x0F0F0F0F0F0F0F0F)) << np.uint64(4))
+    return x.byteswap() >> np.uint64(64 - 2 * k)
+
+
+def canonical_keys_of(keys, k):
+    keys = np.asarray(keys, dtype=np.uint64)
+    return np.minimum(keys, revcomp_keys(keys, k))
+
+
+def all_canonical_keys(k):
+    """every canonical key of k, sorted (4^k candidates: meant for small k)"""
+    x = np.arange(4 ** k, dtype=np.uint64)
+    return x[x <= revcomp_keys(x, k)]
+
+
+def n_canonical(k):
+    return (4 ** k + (4 ** (k // 2) if k % 2 == 0 else 0)) // 2
+
+
+def max_canonical_key(k):
+    """A^(k/2) [C] T^(k/2): the outer bases of a canonical key can at best pair A..T, then the same holds inside"""
+    h = k // 2
+    codes = [0] * h + ([1] if k % 2 else []) + [3] * h
+    return sum(c << (2 * i) for i, c in enumerate(codes))
+
+
+def key_of_codes(codes):
+    return sum(int(c) << (2 * i) for i, c in enumerate(codes))
+
+
+def de_bruijn(k):
+    """B(4, k) as base codes: the Lyndon words over {0..3} whose length divides k, concatenated in lexicographic order
+    (Duval / Fredricksen-Kessler-Maiorana).  Read cyclically, every k-mer occurs exactly once."""
+    seq, w = [], [-1]
+    while w:
+        w[-1] += 1
+        m = len(w)
+        if k % m == 0:
+            seq.extend(w)
+        while len(w) < k:
+            w.append(w[len(w) - m])
+        while w and w[-1] == 3:
+            w.pop()
+    return np.array(seq, dtype=np.uint8)
+
+
+def de_bruijn_linear(k):
+    """B(4, k) followed by its first k - 1 bases again, as ACGT bytes: every k-mer occurs exactly once"""
+    s = de_bruijn(k)
+    return ACGT[np.concatenate([s, s[:k - 1]])].tobytes()
+
+
+def revcomp_bases(seq: bytes):
+    return seq[::-1].translate(bytes.maketrans(b"ACGTacgt", b"TGCAtgca"))
+
+
+def palindromes(k, n, seed):
+    """up to n distinct palindromic k-mers X + revcomp(X) (even k), as ACGT bytes"""
+    assert k % 2 == 0
+    h = k // 2
+    rng = np.random.default_rng(seed)
+    space = 4 ** h
+    if space <= 4096:
+        xs = rng.permutation(space)[:n].tolist()
+    else:
+        xs = list(dict.fromkeys(int(v) for v in rng.integers(0, space, 2 * n, dtype=np.uint64)))[:n]
+    out = []
+    for x in xs:
+        half = ACGT[[(x >> (2 * i)) & 3 for i in range(h)]].tobytes()
+        out.append(half + revcomp_bases(half))
+    return out
+
+
+def plant_palindromes(k, pals, seed, hot_copies=310):
+    """reads that carry each palindrome with ACGT flanks on both sides, with an N on one side, at a read end and alone (so
+    that every edge direction and every missing-neighbour case occurs); the first palindrome also `hot_copies` more times
+    with fixed flanks, so that it and two of its edge counters pass the 8-bit tier"""
+    rng = np.random.default_rng(seed)
+
+    def flank(n):
+        return ACGT[rng.integers(0, 4, n)].tobytes()
+
+    reads = []
+    for i, p in enumerate(pals):
+        both = flank(int(rng.integers(1, 9))) + p + flank(int(rng.integers(1, 9)))
+        reads += [both.lower() if i % 3 == 0 else both,
+                  b"N" + p + flank(int(rng.integers(1, 6))),
+                  flank(int(rng.integers(1, 6))) + p + b"N" + flank(3),
+                  flank(int(rng.integers(1, 6))) + p,
+                  p + flank(int(rng.integers(1, 6))),
+                  p]
+    if pals:
+        reads += [b"A" + pals[0] + b"C"] * hot_copies
+    return reads
+
+
+def hot_kmer_reads(k, seed, copies=320):
+    """one (non-palindromic) k-mer `copies` times with random one-base flanks: a high-copy entry for every k"""
+    rng = np.random.default_rng(seed)
+    while True:
+        kmer = ACGT[rng.integers(0, 4, k)].tobytes()
+        if kmer != revcomp_bases(kmer):
+            break
+    fl = ACGT[rng.integers(0, 4, (copies, 2))]
+    return kmer, [bytes([a]) + kmer + bytes([b]) for a, b in fl.tolist()]
