@@ -204,6 +204,40 @@ void kq_pack_bases(const char* bases, uint64_t len, uint32_t* codes, uint16_t* i
 int  kq_count_packed_dev(kq_handle* h, const uint32_t* d_codes, const uint16_t* d_inv, uint64_t n_bases);
 int  kq_count_packed_async(kq_handle* h, const uint32_t* codes, const uint16_t* inv, uint64_t n_bases, uint64_t* ticket);
 
+/* The same packing on the device: d_bases (ASCII, any alignment) -> d_codes / d_inv (ceil(len / 16) units each), bit-identical
+ * to kq_pack_bases; asynchronous on the handle's stream.  This is how a caller makes the resident packed form of a batch that
+ * kq_count_packed_dev counts (6 bytes per 16 bases of HBM instead of 16) without a host round trip. */
+int  kq_pack_bases_dev(kq_handle* h, const char* d_bases, uint64_t len, uint32_t* d_codes, uint16_t* d_inv);
+
+/* FASTQ / FASTA text on the device (what gfalibs' StreamObj line reader and loadKmers' record walk are to the reference,
+ * src/input.cpp:188-286): the text goes to the GPU as it lies in the file and hand-written kernels find the bases.
+ * `text` holds WHOLE RECORDS: it begins at the first byte of a record and ends at the end of one (a final '\n' is optional);
+ * cutting a file at record starts stays with the caller.  Let l(i) be the number of '\n' before byte i (a '\n' belongs to the
+ * line it ends) and EOL-CR a '\r' directly followed by '\n'.  The read batch is the kept bytes in text order:
+ *   KQ_FASTX_FASTQ  four-line records: byte i is kept iff l(i) mod 4 == 1 and it is no EOL-CR.  The '\n' of a sequence line
+ *                   is the read separator: seq0\nseq1\n...
+ *   KQ_FASTX_FASTA  a line whose first byte is '>' is a header line: only its '\n' is kept (the separator).  Of any other line
+ *                   every byte is kept except '\n' and EOL-CR, so wrapped sequence lines join: \nseq0\nseq1...
+ * (One difference from the host CLI's parser: that one trims every trailing '\r' of a line, this one only the EOL-CR -- "\r\r\n"
+ * inside a wrapped FASTA record ends the run here.)  Positions are 64-bit throughout: no size limit but the memory.
+ * Malformed text is refused, not miscounted: a FASTQ line with l mod 4 == 0 that does not start with '@' or one with
+ * l mod 4 == 2 that does not start with '+' (wrapped records ...), a FASTA text that does not start with '>'.
+ *   kq_parse_fastx_dev   text -> d_bases (room for cap bytes), *n_bases = size of the batch.  Synchronises.  KQ_ERR_CAPACITY
+ *                        (with *n_bases set) when cap is too small; d_bases may be NULL to get *n_bases only; KQ_ERR_INVALID
+ *                        for malformed text (d_bases is unspecified then).
+ *   kq_count_fastx_dev   parse into a library-owned buffer + count, like kq_count_batch_dev of the batch; nothing but the batch
+ *                        size (one 16-byte read, which waits for the stream) returns to the host.
+ *   kq_count_fastx_async text in page-locked host memory -> copy -> parse -> count: same tickets, same threading rule and the
+ *                        same buffer reuse rule as kq_count_batch_async.  The call waits for its own copy and parse (on the
+ *                        copy stream, beside the counting of earlier batches), not for any counting.
+ * Malformed text given to the two count entries is not counted: kq_host_wait of its ticket and every kq_sync up to the next
+ * kq_clear return KQ_ERR_INVALID with a message that names the format; the handle stays usable after kq_clear.
+ * Null pointers or an unknown format: KQ_ERR_INVALID before any device work.  len == 0: KQ_OK, *n_bases = 0. */
+enum { KQ_FASTX_FASTQ = 1, KQ_FASTX_FASTA = 2 };
+int  kq_parse_fastx_dev(kq_handle* h, const char* d_text, uint64_t len, int format, char* d_bases, uint64_t cap, uint64_t* n_bases);
+int  kq_count_fastx_dev(kq_handle* h, const char* d_text, uint64_t len, int format);
+int  kq_count_fastx_async(kq_handle* h, const char* text, uint64_t len, int format, uint64_t* ticket);
+
 /* Hot loop 1 only (DBG::hashSequences :75-113): the (key, edge byte) records of a batch in
  * sequence order; edge byte layout = edgeBit (include/kreeq.h:6-18).  *n_out = number of records
  * (also set on KQ_ERR_CAPACITY).  keys/edges may be NULL to just count. */

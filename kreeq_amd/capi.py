@@ -13,9 +13,12 @@ DBGBASE_DTYPE = np.dtype([("fw", "<u4"), ("bw", "<u4"), ("cov", "<u4"), ("isFw",
 
 # every symbol include/kreeq_amd.h declares
 SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profile", "kq_set_stream", "kq_get_stream", "kq_sync", "kq_flush", "kq_get_info", "kq_last_error",
-           "kq_abi_version", "kq_device_available", "kq_device_memory", "kq_count_batch", "kq_count_batch_dev", "kq_host_alloc", "kq_host_free", "kq_count_batch_async", "kq_host_wait", "kq_pack_bases", "kq_count_packed_dev", "kq_count_packed_async", "kq_emit_records",
+           "kq_abi_version", "kq_device_available", "kq_device_memory", "kq_count_batch", "kq_count_batch_dev", "kq_host_alloc", "kq_host_free", "kq_count_batch_async", "kq_host_wait", "kq_pack_bases", "kq_count_packed_dev", "kq_count_packed_async",
+           "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
            "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_lookup_keys", "kq_branch_scan", "kq_merge", "kq_import", "kq_export"]
+
+FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
 
 
 class KqError(RuntimeError):
@@ -102,6 +105,10 @@ def load():
     L.kq_pack_bases.restype = None
     L.kq_count_packed_dev.argtypes = [vp, vp, vp, u64]
     L.kq_count_packed_async.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
+    L.kq_pack_bases_dev.argtypes = [vp, vp, u64, vp, vp]
+    L.kq_parse_fastx_dev.argtypes = [vp, vp, u64, ci, vp, u64, C.POINTER(u64)]
+    L.kq_count_fastx_dev.argtypes = [vp, vp, u64, ci]
+    L.kq_count_fastx_async.argtypes = [vp, vp, u64, ci, C.POINTER(u64)]
     L.kq_emit_records.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.kq_emit_partitioned_dev.argtypes = [vp, vp, u64, ci, vp, vp, u64, vp]
     L.kq_emit_packed_dev.argtypes = [vp, vp, u64, ci, vp, u64, vp]
@@ -224,6 +231,33 @@ class KreeqDB:
         """pipelined ingest of a 2-bit packed batch (pack_bases); returns the ticket to wait on before the arrays are refilled"""
         t = C.c_uint64(0)
         _check(load().kq_count_packed_async(self._h, C.c_void_p(codes_ptr), C.c_void_p(inv_ptr), n_bases, C.byref(t)))
+        return t.value
+
+    def pack_bases_dev(self, bases_ptr, n, codes_ptr, inv_ptr):
+        """device ASCII -> the packed form (kq_pack_bases' layout: ceil(n / 16) u32 + u16), asynchronous on the handle's stream"""
+        _check(load().kq_pack_bases_dev(self._h, C.c_void_p(bases_ptr), n, C.c_void_p(codes_ptr), C.c_void_p(inv_ptr)))
+
+    def parse_fastx_dev(self, text_ptr, n, fmt, out_ptr, cap):
+        """device FASTQ / FASTA text (whole records) -> the read batch at out_ptr (room for cap bytes); returns its size.
+        out_ptr None / 0: the size only.  Raises KqError -6 when cap is too small (KqError.needed holds the size), -1 for
+        malformed text"""
+        nb = C.c_uint64(0)
+        rc = load().kq_parse_fastx_dev(self._h, C.c_void_p(text_ptr), n, fmt, C.c_void_p(out_ptr) if out_ptr else None, cap, C.byref(nb))
+        if rc != 0:
+            e = KqError(rc, load().kq_last_error().decode(errors="replace"))
+            e.needed = nb.value
+            raise e
+        return nb.value
+
+    def count_fastx_dev(self, text_ptr, n, fmt):
+        """parse device text + count it, like count_batch_dev of its read batch"""
+        _check(load().kq_count_fastx_dev(self._h, C.c_void_p(text_ptr), n, fmt))
+
+    def count_fastx_async(self, host_ptr, n, fmt):
+        """pipelined ingest of raw FASTQ / FASTA text (pinned memory from host_alloc): copy, parse and count on the device;
+        returns the ticket to wait on before the buffer is refilled (host_wait raises for malformed text)"""
+        t = C.c_uint64(0)
+        _check(load().kq_count_fastx_async(self._h, C.c_void_p(host_ptr), n, fmt, C.byref(t)))
         return t.value
 
     def host_wait(self, ticket):

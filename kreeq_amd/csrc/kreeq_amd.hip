@@ -24,6 +24,7 @@
 using namespace kq;
 
 #include "kq_kernels.h"
+#include "kq_fastx.h"
 
 // ================================================================================================
 // host side
@@ -186,6 +187,17 @@ struct kq_handle {
     std::vector<hipEvent_t> in_copied;   // ring of "copy of ticket t done" events
     uint64_t in_next = 0;
     std::mutex in_m;                     // kq_count_batch_async may be called from several threads: the calls take turns
+    uint8_t in_bad[IN_TICKETS] = {};     // format (KQ_FASTX_*) whose rules the text of a ticket broke (kq_count_fastx_async), else 0
+    // device FASTQ / FASTA parser (kq_fastx.h): unit summaries, the compact read batch of kq_count_fastx_dev and, per ring
+    // slot, of kq_count_fastx_async (the slot's in_buf keeps the raw text), the chain's result and its page-locked mirror
+    void* fx_units = nullptr; size_t fx_units_bytes = 0;
+    void* fx_out = nullptr; size_t fx_out_bytes = 0;
+    void* in_cmp[IN_SLOTS] = {nullptr, nullptr, nullptr}; size_t in_cmp_bytes[IN_SLOTS] = {0, 0, 0};
+    FxResult* fx_res = nullptr;          // device
+    FxResult* fx_res_host = nullptr;     // pinned
+    int fx_bad = 0;                      // a counted text broke its format: reported by kq_sync until kq_clear
+    bool hist_cache_off = false;         // the batch being counted lives in a library-owned buffer, which keeps its address and
+                                         // changes its content: the address-keyed KQ_OPT_COUNT_MAP_PASSES cache must not see it
     bool test_fail_plan = false;         // KQ_OPT_TEST_FAIL_PLAN: the next partition plan fails with KQ_ERR_NOMEM (failure-path tests)
     void* hot = nullptr; size_t hot_bytes = 0;         // k_count_regions' list of skewed regions
 
@@ -555,6 +567,11 @@ void kq_destroy(kq_handle* h) {
     if (h->ev_pass) (void)hipEventDestroy(h->ev_pass);
     for (int i = 0; i < kq_handle::IN_SLOTS; ++i) { if (h->in_buf[i]) (void)hipFree(h->in_buf[i]); if (h->in_consumed[i]) (void)hipEventDestroy(h->in_consumed[i]); }
     for (auto e : h->in_copied) (void)hipEventDestroy(e);
+    for (int i = 0; i < kq_handle::IN_SLOTS; ++i) if (h->in_cmp[i]) (void)hipFree(h->in_cmp[i]);
+    if (h->fx_units) (void)hipFree(h->fx_units);
+    if (h->fx_out) (void)hipFree(h->fx_out);
+    if (h->fx_res) (void)hipFree(h->fx_res);
+    if (h->fx_res_host) (void)hipHostFree(h->fx_res_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     arena_release(h);
     if (h->d_sets) (void)hipFree(h->d_sets);
@@ -575,6 +592,7 @@ int kq_clear(kq_handle* h) {
     h->hc_check_at = 0;
     h->table_empty = true;
     h->n_pend = 0; h->arena_used = 0; h->pend_records = 0;      // records not applied yet are dropped with the rest
+    h->fx_bad = 0;
     return KQ_OK;
 }
 
@@ -658,7 +676,9 @@ int kq_sync(kq_handle* h) {
     if (!h) return fail(KQ_ERR_INVALID, "null handle");
     HIPC(hipSetDevice(h->device));
     HIPC(hipStreamSynchronize(h->stream));
-    return check_errors(h);
+    const int rc = check_errors(h);
+    if (h->fx_bad) return fail(KQ_ERR_INVALID, "malformed %s text was submitted for counting and skipped (kq_clear resets this)", h->fx_bad == KQ_FASTX_FASTQ ? "FASTQ" : "FASTA");
+    return rc;
 }
 int kq_flush(kq_handle* h) {
     if (!h) return fail(KQ_ERR_INVALID, "null handle");
@@ -808,7 +828,7 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     // launch (bin = range * 256 + bucket: the block of a range is contiguous in the bin-major matrix) and keeps the raw counts;
     // every pass takes its block from there -- (n - 1) of the n histogram scans of a slice are never run.
     bool have_hist = false;
-    if (narrow_filt && h->map_passes > 1 && P1_F == 1) {
+    if (narrow_filt && h->map_passes > 1 && P1_F == 1 && !h->hist_cache_off) {
         const uint32_t n = (uint32_t)h->map_passes, per = cfg.map_count / n, rr = cfg.filt_lo / per;
         if (cfg.filt_lo == rr * per && cfg.filt_hi == (rr + 1) * per) {
             const kq_handle::HistKey key{ab, pinv, lead, len, er.lo, er.hi, p->g1, n, h->k};
@@ -835,7 +855,7 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     }
     // the same for bucket-range passes (windowed table): the unfiltered bucket matrix serves every window -- the rows of the
     // other buckets are zeroed before the scan
-    if (narrow_win && h->map_passes > 1 && P1_F == 1) {
+    if (narrow_win && h->map_passes > 1 && P1_F == 1 && !h->hist_cache_off) {
         const kq_handle::HistKey key{ab, pinv, lead, len, er.lo, er.hi, p->g1, 0xB0C4E7u, h->k};
         const size_t block = (size_t)(1u << NARROW_CBITS) * p->g1 * sizeof(unsigned long long), row = (size_t)p->g1 * sizeof(unsigned long long);
         kq_handle::HistEntry* ent = nullptr;
@@ -1403,12 +1423,8 @@ void* kq_host_alloc(uint64_t bytes) {
 }
 void kq_host_free(void* p) { if (p) { (void)hipHostUnregister(p); free(p); } }
 
-// shared by the ASCII and the packed entry point: copy (a [+ b]) into a staging slot, count behind the copy
-static int ingest_async(kq_handle* h, const void* a, size_t a_bytes, const void* b, size_t b_bytes, uint64_t n_bases, uint64_t* ticket) {
-    HIPC(hipSetDevice(h->device));
-    // One caller at a time, copy included: concurrent copies from pageable memory on several streams were measured and are
-    // 3 x SLOWER than one after the other (HIP stages them through per-stream buffers it first has to set up)
-    std::lock_guard<std::mutex> lock(h->in_m);
+// A ticket and its staging slot (under h->in_m): the copy stream waits for the slot's previous reader, the slot holds `bytes`
+static int ingest_begin(kq_handle* h, size_t bytes, uint64_t* ticket, int* slot, hipEvent_t* copied) {
     if (!h->copy_stream) {
         HIPC(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
         for (int i = 0; i < kq_handle::IN_SLOTS; ++i) HIPC(hipEventCreateWithFlags(&h->in_consumed[i], hipEventDisableTiming));
@@ -1417,11 +1433,11 @@ static int ingest_async(kq_handle* h, const void* a, size_t a_bytes, const void*
     }
     const uint64_t t = h->in_next++;
     const int s = (int)(t % kq_handle::IN_SLOTS);
-    hipEvent_t copied = h->in_copied[t % kq_handle::IN_TICKETS];
-    *ticket = t;
+    *copied = h->in_copied[t % kq_handle::IN_TICKETS];
+    *ticket = t; *slot = s;
+    h->in_bad[t % kq_handle::IN_TICKETS] = 0;
     // the slot's previous reader must be done before it is overwritten (copy stream waits; the host does not)
     if (t >= (uint64_t)kq_handle::IN_SLOTS) HIPC(hipStreamWaitEvent(h->copy_stream, h->in_consumed[s], 0));
-    const size_t b_off = (a_bytes + 63) & ~(size_t)63, bytes = b_off + b_bytes;
     if (h->in_bytes[s] < bytes + 64) {
         // growing a slot: nothing may still read the old buffer
         if (h->in_buf[s]) { HIPC(hipStreamSynchronize(h->copy_stream)); HIPC(hipStreamSynchronize(h->stream)); HIPC(hipFree(h->in_buf[s])); h->in_buf[s] = nullptr; h->in_bytes[s] = 0; }
@@ -1429,12 +1445,24 @@ static int ingest_async(kq_handle* h, const void* a, size_t a_bytes, const void*
         HIPC(hipMalloc(&h->in_buf[s], want));
         h->in_bytes[s] = want;
     }
+    return KQ_OK;
+}
+// shared by the ASCII and the packed entry point: copy (a [+ b]) into a staging slot, count behind the copy
+static int ingest_async(kq_handle* h, const void* a, size_t a_bytes, const void* b, size_t b_bytes, uint64_t n_bases, uint64_t* ticket) {
+    HIPC(hipSetDevice(h->device));
+    // One caller at a time, copy included: concurrent copies from pageable memory on several streams were measured and are
+    // 3 x SLOWER than one after the other (HIP stages them through per-stream buffers it first has to set up)
+    std::lock_guard<std::mutex> lock(h->in_m);
+    const size_t b_off = (a_bytes + 63) & ~(size_t)63, bytes = b_off + b_bytes;
+    int s = 0; hipEvent_t copied;
+    int rc = ingest_begin(h, bytes, ticket, &s, &copied);
+    if (rc) return rc;
     char* d = (char*)h->in_buf[s];
     if (a_bytes) HIPC(hipMemcpyAsync(d, a, a_bytes, hipMemcpyHostToDevice, h->copy_stream));
     if (b_bytes) HIPC(hipMemcpyAsync(d + b_off, b, b_bytes, hipMemcpyHostToDevice, h->copy_stream));
     HIPC(hipEventRecord(copied, h->copy_stream));
     HIPC(hipStreamWaitEvent(h->stream, copied, 0));
-    int rc = count_seq_dev(h, d, b ? (const uint16_t*)(d + b_off) : nullptr, n_bases);
+    rc = count_seq_dev(h, d, b ? (const uint16_t*)(d + b_off) : nullptr, n_bases);
     HIPC(hipEventRecord(h->in_consumed[s], h->stream));
     return rc;
 }
@@ -1453,7 +1481,144 @@ int kq_host_wait(kq_handle* h, uint64_t ticket) {
     if (ticket >= h->in_next) return fail(KQ_ERR_INVALID, "unknown ticket %llu", (unsigned long long)ticket);
     if (h->in_next - ticket >= (uint64_t)kq_handle::IN_TICKETS) return KQ_OK;      // long recycled: that copy finished many batches ago
     HIPC(hipEventSynchronize(h->in_copied[ticket % kq_handle::IN_TICKETS]));
+    if (const int bad = h->in_bad[ticket % kq_handle::IN_TICKETS])
+        return fail(KQ_ERR_INVALID, "malformed %s text (ticket %llu): not counted", bad == KQ_FASTX_FASTQ ? "FASTQ" : "FASTA", (unsigned long long)ticket);
     return KQ_OK;
+}
+
+// ---- FASTQ / FASTA text and 2-bit packing on the device (kq_fastx.h) --------------------------------------------------
+
+int kq_pack_bases_dev(kq_handle* h, const char* d_bases, uint64_t len, uint32_t* d_codes, uint16_t* d_inv) {
+    if (!h || ((!d_bases || !d_codes || !d_inv) && len)) return fail(KQ_ERR_INVALID, "null argument");
+    if (!len) return KQ_OK;
+    HIPC(hipSetDevice(h->device));
+    const uint8_t* ab; uint64_t lead;
+    aligned_view(d_bases, &ab, &lead);
+    hipLaunchKernelGGL(k_pack_bases, dim3(grid_for(h, (len + 15) / 16, 256, 16)), dim3(256), 0, h->stream, ab, (uint32_t)lead, len, d_codes, d_inv);
+    HIPC(hipGetLastError());
+    return KQ_OK;
+}
+
+static int fx_args(kq_handle* h, const char* text, uint64_t len, int format) {
+    if (!h || (!text && len)) return fail(KQ_ERR_INVALID, "null argument");
+    if (format != KQ_FASTX_FASTQ && format != KQ_FASTX_FASTA) return fail(KQ_ERR_INVALID, "format must be KQ_FASTX_FASTQ or KQ_FASTX_FASTA, not %d", format);
+    return KQ_OK;
+}
+static uint64_t fx_units_of(const char* d_text, uint64_t len) { return (((uintptr_t)d_text & 15) + len + FX_UNIT - 1) / FX_UNIT; }
+static int fx_prepare(kq_handle* h, uint64_t n_units) {
+    if (!h->fx_res) HIPC(hipMalloc((void**)&h->fx_res, sizeof(FxResult)));
+    if (!h->fx_res_host) HIPC(hipHostMalloc((void**)&h->fx_res_host, sizeof(FxResult), hipHostMallocDefault));
+    return ensure_buf(&h->fx_units, &h->fx_units_bytes, (size_t)n_units * sizeof(FxUnit));
+}
+// summaries + scan on `st` (len > 0): the units hold every unit's output offset and incoming state, fx_res the total
+static void fx_scan(kq_handle* h, hipStream_t st, const char* d_text, uint64_t len, int format) {
+    const uint8_t* ab; uint64_t lead;
+    aligned_view(d_text, &ab, &lead);
+    const uint64_t n_units = fx_units_of(d_text, len);
+    const dim3 grid((unsigned)((n_units + FX_THREADS / 64 - 1) / (FX_THREADS / 64)));
+    FxUnit* units = (FxUnit*)h->fx_units;
+    if (format == KQ_FASTX_FASTQ) {
+        hipLaunchKernelGGL((k_fx_summary<FX_FASTQ>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, units);
+        hipLaunchKernelGGL((k_fx_scan<FX_FASTQ>), dim3(1), dim3(FX_SCAN_THREADS), 0, st, ab, lead, units, n_units, h->fx_res);
+    } else {
+        hipLaunchKernelGGL((k_fx_summary<FX_FASTA>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, units);
+        hipLaunchKernelGGL((k_fx_scan<FX_FASTA>), dim3(1), dim3(FX_SCAN_THREADS), 0, st, ab, lead, units, n_units, h->fx_res);
+    }
+}
+// kept bytes -> d_out (nullptr: the record checks only)
+static void fx_apply(kq_handle* h, hipStream_t st, const char* d_text, uint64_t len, int format, char* d_out) {
+    const uint8_t* ab; uint64_t lead;
+    aligned_view(d_text, &ab, &lead);
+    const uint64_t n_units = fx_units_of(d_text, len);
+    const dim3 grid((unsigned)((n_units + FX_THREADS / 64 - 1) / (FX_THREADS / 64)));
+    if (format == KQ_FASTX_FASTQ) hipLaunchKernelGGL((k_fx_apply<FX_FASTQ>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, (const FxUnit*)h->fx_units, (uint8_t*)d_out, h->fx_res);
+    else hipLaunchKernelGGL((k_fx_apply<FX_FASTA>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, (const FxUnit*)h->fx_units, (uint8_t*)d_out, h->fx_res);
+}
+static int fx_read_result(kq_handle* h, hipStream_t st) {
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(h->fx_res_host, h->fx_res, sizeof(FxResult), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return KQ_OK;
+}
+static const char* fx_name(int format) { return format == KQ_FASTX_FASTQ ? "FASTQ" : "FASTA"; }
+static const char* fx_rule(int format) {
+    return format == KQ_FASTX_FASTQ ? "four-line records expected: every first line starts with '@', every third with '+'" : "the text must start with '>'";
+}
+
+int kq_parse_fastx_dev(kq_handle* h, const char* d_text, uint64_t len, int format, char* d_bases, uint64_t cap, uint64_t* n_bases) {
+    int rc = fx_args(h, d_text, len, format);
+    if (rc) return rc;
+    if (!n_bases) return fail(KQ_ERR_INVALID, "null argument");
+    *n_bases = 0;
+    if (!len) return KQ_OK;
+    HIPC(hipSetDevice(h->device));
+    rc = fx_prepare(h, fx_units_of(d_text, len)); if (rc) return rc;
+    fx_scan(h, h->stream, d_text, len, format);
+    rc = fx_read_result(h, h->stream); if (rc) return rc;
+    const uint64_t n = h->fx_res_host->n_bases;
+    *n_bases = n;
+    const bool fits = d_bases && n <= cap;
+    fx_apply(h, h->stream, d_text, len, format, fits ? d_bases : nullptr);
+    rc = fx_read_result(h, h->stream); if (rc) return rc;
+    if (h->fx_res_host->bad) return fail(KQ_ERR_INVALID, "malformed %s text (%s)", fx_name(format), fx_rule(format));
+    if (d_bases && !fits) return fail(KQ_ERR_CAPACITY, "output buffer too small: %llu bases, room for %llu", (unsigned long long)n, (unsigned long long)cap);
+    return KQ_OK;
+}
+
+// counts out of a library-owned buffer: no KQ_OPT_COUNT_MAP_PASSES cache entry may be made for or taken from its address
+struct HistCacheOff { kq_handle* h; explicit HistCacheOff(kq_handle* x) : h(x) { h->hist_cache_off = true; } ~HistCacheOff() { h->hist_cache_off = false; } };
+
+int kq_count_fastx_dev(kq_handle* h, const char* d_text, uint64_t len, int format) {
+    int rc = fx_args(h, d_text, len, format);
+    if (rc) return rc;
+    if (!len) return KQ_OK;
+    HIPC(hipSetDevice(h->device));
+    rc = fx_prepare(h, fx_units_of(d_text, len)); if (rc) return rc;
+    if (h->fx_out_bytes < len + 64) {
+        HIPC(hipStreamSynchronize(h->stream));             // (an earlier count may still read the old buffer)
+        rc = ensure_buf(&h->fx_out, &h->fx_out_bytes, len + 64); if (rc) return rc;
+    }
+    fx_scan(h, h->stream, d_text, len, format);
+    fx_apply(h, h->stream, d_text, len, format, (char*)h->fx_out);
+    // the count path plans its slices and scratch from the batch size on the host: one 16-byte read per call
+    rc = fx_read_result(h, h->stream); if (rc) return rc;
+    if (h->fx_res_host->bad) { h->fx_bad = format; return KQ_OK; }       // not counted; kq_sync reports it
+    HistCacheOff guard(h);
+    return count_seq_dev(h, (const char*)h->fx_out, nullptr, h->fx_res_host->n_bases);
+}
+
+int kq_count_fastx_async(kq_handle* h, const char* text, uint64_t len, int format, uint64_t* ticket) {
+    int rc = fx_args(h, text, len, format);
+    if (rc) return rc;
+    if (!ticket) return fail(KQ_ERR_INVALID, "null argument");
+    if (!len) return ingest_async(h, nullptr, 0, nullptr, 0, 0, ticket);
+    HIPC(hipSetDevice(h->device));
+    std::lock_guard<std::mutex> lock(h->in_m);
+    int s = 0; hipEvent_t copied;
+    rc = ingest_begin(h, len, ticket, &s, &copied); if (rc) return rc;
+    if (h->in_cmp_bytes[s] < len + 64) {
+        if (h->in_cmp[s]) { HIPC(hipStreamSynchronize(h->copy_stream)); HIPC(hipStreamSynchronize(h->stream)); }
+        rc = ensure_buf(&h->in_cmp[s], &h->in_cmp_bytes[s], len + 64); if (rc) return rc;
+    }
+    rc = fx_prepare(h, fx_units_of((const char*)h->in_buf[s], len)); if (rc) return rc;
+    // copy and parse on the copy stream: beside the counting of earlier batches.  The call waits for ITS OWN copy and parse
+    // (the batch size plans the count on the host), never for the counting of earlier batches unless the ring is full
+    char* d = (char*)h->in_buf[s];
+    HIPC(hipMemcpyAsync(d, text, len, hipMemcpyHostToDevice, h->copy_stream));
+    HIPC(hipEventRecord(copied, h->copy_stream));
+    fx_scan(h, h->copy_stream, d, len, format);
+    fx_apply(h, h->copy_stream, d, len, format, (char*)h->in_cmp[s]);
+    rc = fx_read_result(h, h->copy_stream); if (rc) return rc;
+    if (h->fx_res_host->bad) {
+        h->in_bad[*ticket % kq_handle::IN_TICKETS] = (uint8_t)format;
+        h->fx_bad = format;
+        rc = KQ_OK;
+    } else {
+        HistCacheOff guard(h);
+        rc = count_seq_dev(h, (const char*)h->in_cmp[s], nullptr, h->fx_res_host->n_bases);
+    }
+    HIPC(hipEventRecord(h->in_consumed[s], h->stream));
+    return rc;
 }
 
 static int emit_ordered(kq_handle* h, const char* d_bases, uint64_t len, uint64_t* d_keys, uint8_t* d_edges, uint64_t cap,

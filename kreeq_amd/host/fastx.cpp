@@ -438,4 +438,108 @@ void read_batches_sink(const std::string& path, unsigned threads, const BatchSin
     if (failed) throw std::runtime_error(first_error);
 }
 
+void read_raw_sink(const std::string& path, unsigned threads, const RawSink& sink) {
+    if (threads < 1) threads = 1;
+    struct stat st;
+    const bool gz = path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0;
+    int fd = -1;
+    const char* data = nullptr;
+    size_t size = 0;
+    if (!gz && stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+        fd = open(path.c_str(), O_RDONLY);
+        if (fd >= 0) {
+            void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m != MAP_FAILED) { data = (const char*)m; size = (size_t)st.st_size; madvise(m, size, MADV_SEQUENTIAL); }
+        }
+    }
+    if (!data || (data[0] != '@' && data[0] != '>') || !sink.submit_raw) {
+        // compressed / piped / unknown: the records are walked on the host
+        if (data) munmap((void*)data, size);
+        if (fd >= 0) close(fd);
+        read_batches_sink(path, threads, sink);
+        return;
+    }
+    const bool fastq = data[0] == '@';
+    const char* begin = data;
+    const char* end = data + size;
+    const size_t chunk = std::max<size_t>((size_t)4 << 20, std::min<size_t>((size_t)32 << 20, size / (threads * 4) + 1));
+    const size_t n_chunks = (size + chunk - 1) / chunk;
+    std::mutex next_m;
+    size_t next_chunk = 0;
+    std::string first_error;
+    bool failed = false;
+    auto sync = [&](const char* p) { return fastq ? fastq_sync(p, begin, end) : fasta_sync(p, begin, end); };
+    auto worker = [&](unsigned t) {
+        Appender ap(sink, t);                              // only for records that do not fit a pool buffer
+        try {
+            for (;;) {
+                size_t c;
+                { std::lock_guard<std::mutex> l(next_m); if (failed) break; c = next_chunk++; }
+                if (c >= n_chunks) break;
+                const char* lo = begin + c * chunk;
+                const char* hi = std::min(end, lo + chunk);
+                // the records whose first byte lies in [lo, hi): from the first record start at or after lo to the first at or after hi
+                const char* p = sync(lo);
+                if (c == 0 && p != begin) throw std::runtime_error("malformed " + std::string(fastq ? "FASTQ" : "FASTA") + " record at the start of " + path);
+                const char* stop = hi < end ? sync(hi) : end;
+                while (p < stop) {
+                    size_t cap = 0;
+                    char* buf = sink.acquire(t, &cap);
+                    // the longest run of whole records from p that fits the buffer, looked for at a few distances (a record
+                    // start is found forwards only): nearly a buffer, half of one, the next record
+                    const char* q = stop;
+                    if ((size_t)(stop - p) > cap) {
+                        q = nullptr;
+                        for (size_t off : {cap - cap / 16, cap / 2, (size_t)1}) {
+                            if (off < 1 || off >= (size_t)(stop - p)) continue;
+                            const char* cand = std::min(stop, sync(p + off));
+                            if ((size_t)(cand - p) <= cap) { q = cand; break; }
+                        }
+                    }
+                    if (q) {
+                        memcpy(buf, p, (size_t)(q - p));
+                        sink.submit_raw(t, buf, (size_t)(q - p), fastq);
+                        p = q;
+                        continue;
+                    }
+                    // one record longer than a pool buffer: the buffer goes back empty, the record is parsed here
+                    sink.submit(t, buf, 0);
+                    const char* seq = next_line(p, end);
+                    if (fastq) {
+                        const char* plus = next_line(seq, end);
+                        const char* qual = next_line(plus, end);
+                        if (*p != '@' || (plus < end && *plus != '+'))
+                            throw std::runtime_error("malformed FASTQ record (four-line records expected) at byte " + std::to_string((size_t)(p - begin)) + " of " + path);
+                        const char* e = trim_eol(seq, plus);
+                        ap.reserve((size_t)(e - seq));
+                        ap.begin();
+                        ap.piece(seq, e);
+                        p = next_line(qual, end);
+                    } else {
+                        const char* nxt = seq;
+                        size_t total = 0;
+                        while (nxt < end && *nxt != '>') { const char* e = next_line(nxt, end); total += (size_t)(trim_eol(nxt, e) - nxt); nxt = e; }
+                        ap.reserve(total);
+                        ap.begin();
+                        for (const char* s = seq; s < nxt;) { const char* e = next_line(s, nxt); ap.piece(s, trim_eol(s, e)); s = e; }
+                        p = nxt;
+                    }
+                    ap.flush();
+                }
+            }
+            ap.flush();
+        } catch (const std::exception& e) {
+            bool first = false;
+            { std::lock_guard<std::mutex> l(next_m); if (!failed) { failed = true; first = true; first_error = e.what(); } }
+            if (first && sink.abort) sink.abort();
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < threads; ++t) pool.emplace_back(worker, t);
+    for (auto& t : pool) t.join();
+    munmap((void*)data, size);
+    close(fd);
+    if (failed) throw std::runtime_error(first_error);
+}
+
 }  // namespace kqhost

@@ -47,4 +47,16 @@ struct BatchSink {
 };
 void read_batches_sink(const std::string& path, unsigned threads, const BatchSink& sink);
 
+// Raw-range variant for the device parser (kq_count_fastx_async, include/kreeq_amd.h): for a plain (mmap'ed) FASTQ / FASTA
+// file the parser threads do NOT walk the records.  A thread finds the record-aligned byte range of its chunk, cuts it at
+// record starts into pieces that fit a pool buffer, copies each piece AS TEXT into a buffer from sink.acquire and hands it to
+//   submit_raw(thread, buf, len, fastq)   buf holds len bytes of whole records, FASTQ (fastq = true) or FASTA
+// A record that does not fit a pool buffer on its own (a chromosome of a FASTA given as reads) is parsed on the host and
+// travels through acquire / acquire_big / submit / submit_big like in read_batches_sink, whole, so its k-mers are not cut.
+// Input that cannot be mapped (.gz, pipes) goes through read_batches_sink unchanged: submit_raw is never called for it.
+struct RawSink : BatchSink {
+    std::function<void(unsigned thread, char* buf, size_t len, bool fastq)> submit_raw;
+};
+void read_raw_sink(const std::string& path, unsigned threads, const RawSink& sink);
+
 }  // namespace kqhost

@@ -327,6 +327,7 @@ struct GpuSink {
     kq_handle* h;
     size_t cap;
     bool packed;
+    bool device_parse = false;                    // KQ_INGEST_DEVICE: plain files travel as raw text, the records are found on the GPU (kq_count_fastx_async)
     struct Buf { char* ascii = nullptr; uint32_t* codes = nullptr; uint16_t* inv = nullptr; uint64_t ticket = 0; bool in_flight = false; };
     std::vector<Buf> pool;
     std::vector<int> free_list;                   // indices of buffers nobody holds
@@ -334,8 +335,9 @@ struct GpuSink {
     std::mutex m;
     std::condition_variable cv;
     bool failed = false;                          // a parser thread or a submit has failed: nobody waits for a buffer any more (under m)
-    std::atomic<long long> ns_wait{0}, ns_pack{0}, ns_call{0}, n_submit{0};     // KQ_INGEST_TRACE: where the threads spend their time
-    GpuSink(kq_handle* handle, unsigned n_buffers, size_t buffer_bytes, bool pack) : h(handle), cap(buffer_bytes), packed(pack), pool(n_buffers) {
+    std::atomic<long long> ns_wait{0}, ns_pack{0}, ns_call{0}, n_submit{0}, n_dev_submit{0};     // KQ_INGEST_TRACE: where the threads spend their time
+    GpuSink(kq_handle* handle, unsigned n_buffers, size_t buffer_bytes, bool pack, bool dev_parse = false)
+        : h(handle), cap(buffer_bytes), packed(pack && !dev_parse), device_parse(dev_parse), pool(n_buffers) {
         for (unsigned i = 0; i < n_buffers; ++i) free_list.push_back((int)(n_buffers - 1 - i));
     }
     // a buffer gets its memory from the thread that first takes it: the page locking of the pool runs in parallel
@@ -357,8 +359,36 @@ struct GpuSink {
         drain();
         for (auto& b : pool) { if (packed) free(b.ascii); else kq_host_free(b.ascii); kq_host_free(b.codes); kq_host_free(b.inv); }
     }
-    BatchSink sink() {
-        BatchSink bs;
+    // raw_fmt: 0 = buf holds '\n'-separated sequences, KQ_FASTX_* = raw text of whole records (device parser)
+    void submit_buf(char* buf, size_t len, int raw_fmt) {
+        int i = 0;
+        while (pool[i].ascii != buf) ++i;
+        Buf& b = pool[i];
+        const auto t0 = std::chrono::steady_clock::now();
+        if (packed && !raw_fmt) kq_pack_bases(buf, len, b.codes, b.inv);
+        const auto t1 = std::chrono::steady_clock::now();
+        // no lock around the call: kq_count_*_async may be called from several threads (they take turns inside the library)
+        int rc = !len ? KQ_OK : raw_fmt ? kq_count_fastx_async(h, buf, len, raw_fmt, &b.ticket) : packed ? kq_count_packed_async(h, b.codes, b.inv, len, &b.ticket) : kq_count_batch_async(h, buf, len, &b.ticket);
+        static const long fail_after = getenv("KQ_TEST_FAIL_SUBMIT") ? atol(getenv("KQ_TEST_FAIL_SUBMIT")) : -1;      // failure-path test: every submit from the n-th on fails
+        const bool injected = rc == KQ_OK && len && fail_after >= 0 && n_submit.load() >= fail_after;
+        if (injected) { (void)kq_host_wait(h, b.ticket); rc = KQ_ERR_NOMEM; }
+        if (rc != KQ_OK || !len) {
+            // a failed submit (out of device memory at scale ...) or a buffer that was taken and not filled: the buffer goes
+            // back to the pool; on failure every thread waiting for a buffer is woken and throws (they used to
+            // wait forever for buffers held by threads that had died)
+            const std::string err = injected ? "submit failed (injected by KQ_TEST_FAIL_SUBMIT)" : rc != KQ_OK ? kq_last_error() : "";
+            { std::lock_guard<std::mutex> l(m); free_list.push_back(i); if (rc != KQ_OK) failed = true; }
+            cv.notify_all();
+            if (rc != KQ_OK) throw std::runtime_error("Error: " + err);
+            return;
+        }
+        ns_pack += (t1 - t0).count(); ns_call += (std::chrono::steady_clock::now() - t1).count(); ++n_submit; if (raw_fmt) ++n_dev_submit;
+        std::lock_guard<std::mutex> l(m);
+        flying.push_back(i);
+        cv.notify_one();
+    }
+    RawSink sink() {
+        RawSink bs;
         bs.acquire = [this](unsigned, size_t* c) {
             const auto t0 = std::chrono::steady_clock::now();
             std::unique_lock<std::mutex> l(m);
@@ -389,33 +419,8 @@ struct GpuSink {
             *c = cap;
             return pool[i].ascii;
         };
-        bs.submit = [this](unsigned, char* buf, size_t len) {
-            int i = 0;
-            while (pool[i].ascii != buf) ++i;
-            Buf& b = pool[i];
-            const auto t0 = std::chrono::steady_clock::now();
-            if (packed) kq_pack_bases(buf, len, b.codes, b.inv);
-            const auto t1 = std::chrono::steady_clock::now();
-            // no lock around the call: kq_count_*_async may be called from several threads (they take turns inside the library)
-            int rc = !len ? KQ_OK : packed ? kq_count_packed_async(h, b.codes, b.inv, len, &b.ticket) : kq_count_batch_async(h, buf, len, &b.ticket);
-            static const long fail_after = getenv("KQ_TEST_FAIL_SUBMIT") ? atol(getenv("KQ_TEST_FAIL_SUBMIT")) : -1;      // failure-path test: every submit from the n-th on fails
-            const bool injected = rc == KQ_OK && len && fail_after >= 0 && n_submit.load() >= fail_after;
-            if (injected) { (void)kq_host_wait(h, b.ticket); rc = KQ_ERR_NOMEM; }
-            if (rc != KQ_OK || !len) {
-                // a failed submit (out of device memory at scale ...) or a buffer that was taken and not filled: the buffer goes
-                // back to the pool; on failure every thread waiting for a buffer is woken and throws (they used to
-                // wait forever for buffers held by threads that had died)
-                const std::string err = injected ? "submit failed (injected by KQ_TEST_FAIL_SUBMIT)" : rc != KQ_OK ? kq_last_error() : "";
-                { std::lock_guard<std::mutex> l(m); free_list.push_back(i); if (rc != KQ_OK) failed = true; }
-                cv.notify_all();
-                if (rc != KQ_OK) throw std::runtime_error("Error: " + err);
-                return;
-            }
-            ns_pack += (t1 - t0).count(); ns_call += (std::chrono::steady_clock::now() - t1).count(); ++n_submit;
-            std::lock_guard<std::mutex> l(m);
-            flying.push_back(i);
-            cv.notify_one();
-        };
+        if (device_parse) bs.submit_raw = [this](unsigned, char* buf, size_t len, bool fastq) { submit_buf(buf, len, fastq ? KQ_FASTX_FASTQ : KQ_FASTX_FASTA); };
+        bs.submit = [this](unsigned, char* buf, size_t len) { submit_buf(buf, len, 0); };
         // a sequence longer than a pool buffer: a page-locked buffer of its own, submitted like any other and released once
         // its copy has finished (the device side cuts it into slices with overlapping scans: k-mers and edges across a cut
         // are seen exactly once, kreeq_amd.hip count_seq_dev)
@@ -447,6 +452,8 @@ void count_reads_file(kq_handle* h, const std::string& path, unsigned threads, u
     if (const char* e = getenv("KQ_INGEST_CAP_MB")) cap = (size_t)atol(e) << 20;      // tuning aids (tools/bench_extra/cli_ingest_*.py)
     if (const char* e = getenv("KQ_INGEST_BUFFERS")) n_buf = (unsigned)std::max(2, atoi(e));
     if (const char* e = getenv("KQ_INGEST_PACK")) pack = atoi(e) != 0;
+    bool device_parse = false;
+    if (const char* e = getenv("KQ_INGEST_DEVICE")) device_parse = atoi(e) != 0;      // (wins over KQ_INGEST_PACK: the text is packed nowhere, the count reads the parsed batch)
     // A job that knows its size sizes the pending-set arena once (the automatic arena starts small and doubles -- a table
     // pass, a synchronisation and a reallocation every time -- which a 300 MB file pays four or five times): about one k-mer
     // per two input bytes, 5 bytes per record, within half of the free HBM.  Larger inputs just fill it more than once.
@@ -458,16 +465,18 @@ void count_reads_file(kq_handle* h, const std::string& path, unsigned threads, u
         if (!getenv("KQ_CLI_PENDING_AUTO")) kq_or_die(kq_set_option(h, KQ_OPT_PENDING_BYTES, (int64_t)std::min<uint64_t>(want, free_b / 2)));
     }
     const auto t00 = std::chrono::steady_clock::now();
-    GpuSink gs(h, n_buf, cap, pack);
+    GpuSink gs(h, n_buf, cap, pack, device_parse);
     const auto t0 = std::chrono::steady_clock::now();
-    read_batches_sink(path, threads, gs.sink());
+    if (device_parse) read_raw_sink(path, threads, gs.sink());
+    else read_batches_sink(path, threads, gs.sink());
     const auto t1 = std::chrono::steady_clock::now();
     kq_or_die(kq_flush(h));                                          // everything is enqueued; the table pass may start
     gs.drain();                                                      // the last copies out of the pool have finished before it is released
+    if (device_parse) kq_or_die(kq_sync(h));                         // text the device parser refused (malformed FASTQ / FASTA) ends the run here
     if (getenv("KQ_INGEST_TRACE"))
         fprintf(stderr, "ingest: %u threads, %u buffers of %zu MiB, %lld submits, pool %.1f ms, wall %.1f ms + flush %.1f ms; thread-time sums: wait for a buffer %.1f ms, "
-                        "pack %.1f ms, submit calls %.1f ms\n", threads, n_buf, cap >> 20, (long long)gs.n_submit, (t0 - t00).count() * 1e-6, (t1 - t0).count() * 1e-6,
-                (std::chrono::steady_clock::now() - t1).count() * 1e-6, gs.ns_wait * 1e-6, gs.ns_pack * 1e-6, gs.ns_call * 1e-6);
+                        "pack %.1f ms, submit calls %.1f ms; device-parsed submits %lld\n", threads, n_buf, cap >> 20, (long long)gs.n_submit, (t0 - t00).count() * 1e-6, (t1 - t0).count() * 1e-6,
+                (std::chrono::steady_clock::now() - t1).count() * 1e-6, gs.ns_wait * 1e-6, gs.ns_pack * 1e-6, gs.ns_call * 1e-6, (long long)gs.n_dev_submit);
 }
 
 // -j, or one parser thread per 32 MB of input within [4, all cores]: the threads take turns submitting (one stream feeds the

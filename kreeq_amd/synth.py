@@ -125,3 +125,20 @@ def pack_dev(ascii_t, chunk_units=1 << 24):
         codes[lo:hi] = (c << sh2).sum(1, dtype=torch.int32)          # disjoint bit fields: the sum is their OR (wraps into the sign bit)
         inv[lo:hi] = ((~ok).to(torch.int32) << sh1).sum(1, dtype=torch.int32).to(torch.int16)
     return codes, inv
+
+
+def pack_dev_kernel(db, ascii_t):
+    """The same tensors as pack_dev, made by the library's own kernel (kq_pack_bases_dev) on the stream of `db` (a
+    KreeqDB on the tensor's device): one pass over the batch instead of about ten torch ops per chunk, and no
+    temporaries -- 22 bytes of HBM traffic per 16 bases."""
+    import torch
+    dev = ascii_t.device
+    ascii_t = ascii_t.contiguous()
+    n = ascii_t.numel()
+    units = (n + 15) // 16
+    codes = torch.empty(units, dtype=torch.int32, device=dev)
+    inv = torch.empty(units, dtype=torch.int16, device=dev)
+    torch.cuda.synchronize(dev)            # the handle's stream is not torch's: the input is complete, the outputs exist
+    db.pack_bases_dev(ascii_t.data_ptr(), n, codes.data_ptr(), inv.data_ptr())
+    db.sync()
+    return codes, inv
