@@ -201,9 +201,6 @@ __global__ __launch_bounds__(TILE_THREADS, (NBC <= 512 && FMT != FMT_WIDE) ? 3 :
     const uint64_t n_tiles = n_tiles_of(lead, len);
     const uint64_t cols = (uint64_t)gridDim.x * P1_F;
     for (uint32_t b = threadIdx.x; b < cfg.n_coarse; b += MS_THREADS) s.gbase[b] = (uint32_t)m1[(uint64_t)b * cols + (uint64_t)blockIdx.x * P1_F];
-#ifdef KQ_MS_STAMPS
-    if (threadIdx.x == 0) s.stamp_on = 0;
-#endif
     uint4 nxt = tile_fetch(ab, lo_valid, hi_valid, blockIdx.x, pinv);
     landed(nxt.x); landed(nxt.y); landed(nxt.z); landed(nxt.w);         // see k_lv_scatter: keeps the loop header free of a store-draining wait
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -500,9 +497,6 @@ __global__ __launch_bounds__(LV_THREADS, KQ_LV_OCC) void k_lv_scatter(const uint
             const uint32_t first = (b >> lv.nr_shift) * lv.nr_rps + (b & ((1u << lv.nr_shift) - 1u)) * lv.nr_sub;      // narrow_bin's origin; nr_div == 1
             for (uint32_t i = threadIdx.x; i < nb; i += LV_THREADS) s_rst[i] = lv.rstart[first + i];
         }
-#ifdef KQ_MS_STAMPS
-        if (threadIdx.x == 0) { s.stamp_on = 1; s.stamp_last = __builtin_amdgcn_s_memtime(); }
-#endif
         __syncthreads();
         // software pipeline: the next round's records are loaded before this round is split
         // (loads are unconditional, index clamped to the unit: a branch around a load makes the compiler
@@ -701,25 +695,6 @@ __global__ __launch_bounds__(1024) void k_scan_apply(unsigned long long* __restr
 // three-word image of kq_device.h (img_load), all records of the region are applied with LDS atomics (same
 // two-tier rule as table_add), and the image is streamed back (img_store).  Records and slots both hold hash
 // bits, so the walk never reconstructs a key.  Global atomics only for the rare high-copy tier and the two totals.
-#ifdef KQ_STAMPS   // diagnostic build only (never shipped): per-phase cycle sums of k_count_regions
-__device__ unsigned long long g_stamps[8];
-#define KQ_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); \
-                         __builtin_amdgcn_sched_barrier(0); if (threadIdx.x == 0) atomicAdd(&g_stamps[i], t_ - stamp_last); stamp_last = t_; } while (0)
-#endif
-#ifdef KQ_MS_STAMPS
-extern "C" int kq_debug_ms_stamps(unsigned long long* out, int reset) {
-    if (reset) { unsigned long long z[16] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(kq::g_ms_stamps), z, sizeof z); }
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(kq::g_ms_stamps), 128);
-}
-#endif
-#ifdef KQ_STAMPS
-extern "C" int kq_debug_stamps(unsigned long long* out, int reset) {
-    if (reset) { unsigned long long z[8] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof z); }
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), 64);
-}
-#else
-#define KQ_STAMP(i) do { } while (0)
-#endif
 // loads through a pointer that was itself loaded from memory are FLAT loads unless the address space is stated, and a
 // flat load counts on lgkmcnt as well as vmcnt: every LDS wait of the record walk would also wait for the prefetch
 template <class T> __device__ __forceinline__ T ld_global(const T* p) { return *(const __attribute__((address_space(1))) T*)p; }
@@ -752,6 +727,89 @@ struct SetTickets {
     }
 };
 
+// ---- scaffolding shared by the region passes (k_count_regions, k_count_regions_q4) ---------------------------------------
+// The gate of a region visit: builds the wave's tickets and tells whether this workgroup walks region r (block-uniform).
+// A region without records is passed over -- on a lazily cleared table (table_is_empty == 2) after writing its empty image,
+// since that launch initialises every region, also the ones without records.  A region that receives far more records than
+// it has slots goes to hot_list: folding costs a ballot + shuffle per iteration, so only such regions (skew, or very deep
+// coverage) take that path, in the second launch.  HOT = that launch: it walks every listed region.
+template <int THREADS, bool HOT, uint32_t GRP>
+__device__ __forceinline__ bool region_gate(SetTickets<GRP>& tk, const TableView& t, const P3Set* __restrict__ sets, uint32_t n_sets, uint64_t r,
+                                            int table_is_empty, unsigned long long* __restrict__ hot_list /*[0] = count, then region ids*/) {
+    const int tid = threadIdx.x;
+    tk.build(sets, n_sets, r, (uint32_t)tid & 63u);
+    uint64_t n_recs = tk.cnt;                                           // block-uniform after the reduction
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n_recs += __shfl_xor(n_recs, o, 64);
+    if (n_recs == 0) {
+        if (!HOT && table_is_empty == 2) {
+            ulonglong2* g2 = reinterpret_cast<ulonglong2*>(t.slots + (r << REGION_SHIFT));
+            for (int i = tid; i < (int)REGION_SLOTS; i += THREADS) g2[i] = make_ulonglong2(0ull, 0ull);
+        }
+        return false;
+    }
+    if (!HOT && n_recs > 32ull * REGION_SLOTS) {
+        if (tid == 0) hot_list[1 + atomicAdd(&hot_list[0], 1ull)] = r;
+        return false;
+    }
+    return true;
+}
+// High-copy tier of one region, aggregated in LDS (each kernel declares the two arrays): a repeat k-mer with millions of
+// instances would otherwise serialise millions of global atomics on one side-table entry.
+constexpr int HC_LDS = 64;
+__device__ __forceinline__ void hc_lds_reset(uint64_t (&hckey)[HC_LDS], uint32_t (&hccnt)[HC_LDS][8]) {
+    const int tid = threadIdx.x;
+    if (tid < HC_LDS) {
+        hckey[tid] = EMPTY_KEY;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) hccnt[tid][e] = 0;
+    }
+}
+// edge counts e[0..7] of the k-mer with hash h that no longer fit the u8 lanes; global beyond 64 k-mers
+__device__ __forceinline__ void hc_lds_add(const TableView& t, uint64_t (&hckey)[HC_LDS], uint32_t (&hccnt)[HC_LDS][8], uint64_t h, const uint32_t (&e)[8]) {
+    const uint64_t key = key_of_hash(h, t.k);                           // the high-copy tier is keyed by the canonical key
+    int hslot = -1;
+    uint32_t hp = (uint32_t)(h >> 40) & (HC_LDS - 1);
+    for (int probe = 0; probe < HC_LDS; ++probe, hp = (hp + 1) & (HC_LDS - 1)) {
+        uint64_t cur = __hip_atomic_load(&hckey[hp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (cur == EMPTY_KEY) cur = atomicCAS((unsigned long long*)&hckey[hp], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
+        if (cur == EMPTY_KEY || cur == key) { hslot = (int)hp; break; }
+    }
+    if (hslot >= 0) {
+#pragma unroll
+        for (int w = 0; w < 8; ++w) if (e[w]) atomicAdd(&hccnt[hslot][w], e[w]);
+    } else {
+        hc_add(t, h, 0, 0, e);
+    }
+}
+// the region's sums go to the side table: one entry per k-mer (behind the barrier that ends the record walk)
+__device__ __forceinline__ void hc_lds_flush(const TableView& t, uint64_t (&hckey)[HC_LDS], uint32_t (&hccnt)[HC_LDS][8]) {
+    const int tid = threadIdx.x;
+    if (tid < HC_LDS && hckey[tid] != EMPTY_KEY) {
+        HcSlot* hs = hc_upsert(t, hckey[tid]);
+        if (!hs) atomicOr(&t.st->err_hc_full, 1u);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) if (hccnt[tid][e]) atomicAdd((unsigned long long*)&hs->cnt[e], (unsigned long long)hccnt[tid][e]);
+        }
+    }
+}
+// Closing totals of a region visit: every wave adds its slots claimed / instances applied to the LDS sums (in front of the
+// barrier that ends the walk), thread 0 then adds the sums to the table state (in front of the visit's last barrier).
+template <class C>
+__device__ __forceinline__ void region_totals_wave(uint32_t n_new, uint32_t n_ok, C& s_new, C& s_kmers) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { n_new += __shfl_down(n_new, o, 64); n_ok += __shfl_down(n_ok, o, 64); }
+    if ((threadIdx.x & 63) == 0) { if (n_new) atomicAdd(&s_new, (C)n_new); if (n_ok) atomicAdd(&s_kmers, (C)n_ok); }
+}
+template <class C>
+__device__ __forceinline__ void region_totals_store(const TableView& t, const C& s_new, const C& s_kmers) {
+    if (threadIdx.x == 0) {
+        if (s_new) atomicAdd(&t.st->slots_used, (unsigned long long)s_new);
+        if (s_kmers) atomicAdd(&t.st->kmers_added, (unsigned long long)s_kmers);
+    }
+}
+
 #ifndef KQ_P3_THREADS
 #define KQ_P3_THREADS 512
 #define KQ_P3_OCC 6
@@ -777,44 +835,18 @@ __global__ __launch_bounds__(P3_THREADS, HOT ? 4 : KQ_P3_OCC) void k_count_regio
     if (threadIdx.x < 64) s_lut[threadIdx.x] = idx6_to_pack(threadIdx.x);     // visible after the first region's barrier
     __shared__ unsigned long long s_new, s_kmers;
     __shared__ unsigned int s_grp;
-    // high-copy tier of this region, aggregated in LDS: a repeat k-mer with millions of instances
-    // would otherwise serialise millions of global atomics on one side-table entry
-    constexpr int HC_LDS = 64;
-    __shared__ uint64_t s_hckey[HC_LDS];
+    __shared__ uint64_t s_hckey[HC_LDS];      // high-copy tier of this region (hc_lds_*)
     __shared__ uint32_t s_hccnt[HC_LDS][8];
     const int tid = threadIdx.x;
     const uint64_t n_work = HOT ? hot_list[0] : t.reg_hi - t.reg_lo;
-#ifdef KQ_STAMPS
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-#endif
     for (uint64_t w = blockIdx.x; w < n_work; w += gridDim.x) {
         const uint64_t r = HOT ? hot_list[1 + w] : t.reg_lo + w;
-        SetTickets<(uint32_t)GRP> tk;                                   // this region's share of every set (per wave, in registers)
-        tk.build(sets, n_sets, r, (uint32_t)tid & 63u);
-        uint64_t n_recs = tk.cnt;                                       // block-uniform after the reduction
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n_recs += __shfl_xor(n_recs, o, 64);
         const uint32_t narrow_bucket = (NARROW || TOP8) ? (uint32_t)r / narrow_rps : 0u;
         const bool tight = NARROW && aux_fmt == AUX_TIGHT;              // FMT_TIGHT sets: one u32 relative to rstart[r], no lockstep byte
         const uint32_t start_r = tight ? t.rstart[r] : 0u;
-        if (n_recs == 0) {                                              // block-uniform
-            if (!HOT && table_is_empty == 2) {    // lazy kq_clear: this launch initialises every region, also the ones without records
-                ulonglong2* g2 = reinterpret_cast<ulonglong2*>(t.slots + (r << REGION_SHIFT));
-                for (int i = tid; i < (int)REGION_SLOTS; i += P3_THREADS) g2[i] = make_ulonglong2(0ull, 0ull);
-            }
-            continue;
-        }
-        // folding costs a ballot + shuffle per iteration: only regions that receive far more records than
-        // they have slots (skew, or very deep coverage) take that path, in the second launch
-        if (!HOT && n_recs > 32ull * REGION_SLOTS) {
-            if (tid == 0) hot_list[1 + atomicAdd(&hot_list[0], 1ull)] = r;
-            continue;
-        }
-        if (tid < HC_LDS) {
-            s_hckey[tid] = EMPTY_KEY;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s_hccnt[tid][e] = 0;
-        }
+        SetTickets<(uint32_t)GRP> tk;                                   // this region's share of every set (per wave, in registers)
+        if (!region_gate<P3_THREADS, HOT>(tk, t, sets, n_sets, r, table_is_empty, hot_list)) continue;
+        hc_lds_reset(s_hckey, s_hccnt);
         ulonglong2* gimg = reinterpret_cast<ulonglong2*>(t.slots + (r << REGION_SHIFT));
         if (table_is_empty) {            // first batch after kq_create / kq_clear: the image is known, skip the 32 KiB read
             for (int i = tid; i < (int)(REGION_SLOTS * 3); i += P3_THREADS) s_img[i] = (i % 3 == 0) ? EMPTY_KEY : 0ull;
@@ -827,7 +859,6 @@ __global__ __launch_bounds__(P3_THREADS, HOT ? 4 : KQ_P3_OCC) void k_count_regio
         }
         if (tid == 0) { s_new = 0; s_kmers = 0; s_grp = P3_THREADS / 64; }
         __syncthreads();
-        KQ_STAMP(0);                                                    // region_base load + image init/load + barrier
         uint32_t n_new = 0, n_ok = 0;
         // Slot of `key` in the LDS image (word index), claiming an empty one if needed; REGION_SLOTS*3 = not found.
         // The image is read with workgroup-scope relaxed atomic loads on the __shared__ array itself: a
@@ -860,23 +891,8 @@ __global__ __launch_bounds__(P3_THREADS, HOT ? 4 : KQ_P3_OCC) void k_count_regio
             atomicOr(&t.st->err_table_full, 1u);
             return REGION_SLOTS * 3;
         };
-        // edge counts that no longer fit the u8 lanes: the region's LDS high-copy aggregation, global beyond 64 k-mers
-        auto add_wide = [&](uint64_t h, const uint32_t (&e)[8]) {
-            const uint64_t key = key_of_hash(h, t.k);                  // the high-copy tier is keyed by the canonical key
-            int hslot = -1;
-            uint32_t hp = (uint32_t)(h >> 40) & (HC_LDS - 1);
-            for (int probe = 0; probe < HC_LDS; ++probe, hp = (hp + 1) & (HC_LDS - 1)) {
-                uint64_t cur = __hip_atomic_load(&s_hckey[hp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (cur == EMPTY_KEY) cur = atomicCAS((unsigned long long*)&s_hckey[hp], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-                if (cur == EMPTY_KEY || cur == key) { hslot = (int)hp; break; }
-            }
-            if (hslot >= 0) {
-#pragma unroll
-                for (int w = 0; w < 8; ++w) if (e[w]) atomicAdd(&s_hccnt[hslot][w], e[w]);
-            } else {
-                hc_add(t, h, 0, 0, e);
-            }
-        };
+        // edge counts that no longer fit the u8 lanes: the region's LDS high-copy aggregation
+        auto add_wide = [&](uint64_t h, const uint32_t (&e)[8]) { hc_lds_add(t, s_hckey, s_hccnt, h, e); };
         // one record: `pack` holds its (at most two) edge bits, one per byte lane
         auto apply1 = [&](uint64_t h, uint64_t pack) {
             const uint32_t w = find_slot(slot_rem(h, t.k), h);
@@ -999,29 +1015,13 @@ __global__ __launch_bounds__(P3_THREADS, HOT ? 4 : KQ_P3_OCC) void k_count_regio
         if (have_acc && (tid & 63) == 0) apply(acc_key, acc_e, acc_cnt);
         };
         run(std::integral_constant<bool, HOT>{});
-        KQ_STAMP(1);                                                    // record walk
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { n_new += __shfl_down(n_new, o, 64); n_ok += __shfl_down(n_ok, o, 64); }
-        if ((tid & 63) == 0) { if (n_new) atomicAdd(&s_new, (unsigned long long)n_new); if (n_ok) atomicAdd(&s_kmers, (unsigned long long)n_ok); }
+        region_totals_wave(n_new, n_ok, s_new, s_kmers);
         __syncthreads();
-        if (tid < HC_LDS && s_hckey[tid] != EMPTY_KEY) {            // flush the region's high-copy sums: one entry per k-mer
-            HcSlot* hs = hc_upsert(t, s_hckey[tid]);
-            if (!hs) atomicOr(&t.st->err_hc_full, 1u);
-            else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) if (s_hccnt[tid][e]) atomicAdd((unsigned long long*)&hs->cnt[e], (unsigned long long)s_hccnt[tid][e]);
-            }
-        }
-        KQ_STAMP(2);                                                    // barrier (slowest wave) + high-copy flush
+        hc_lds_flush(t, s_hckey, s_hccnt);
 #pragma unroll
         for (int j = 0; j < (int)(REGION_SLOTS / P3_THREADS); ++j) gimg[tid + j * P3_THREADS] = img_store(t, s_img, tid + j * P3_THREADS, r);
-        KQ_STAMP(3);                                                    // image store issue
-        if (tid == 0) {
-            if (s_new) atomicAdd(&t.st->slots_used, s_new);
-            if (s_kmers) atomicAdd(&t.st->kmers_added, s_kmers);
-        }
+        region_totals_store(t, s_new, s_kmers);
         __syncthreads();
-        KQ_STAMP(4);                                                    // final barrier
     }
 }
 
@@ -1031,240 +1031,30 @@ __global__ __launch_bounds__(256) void k_region_starts(uint32_t* __restrict__ ou
         out[r] = r < R ? (uint32_t)(((r << 32) + R - 1) / R) : 0xFFFFFFFFu;
 }
 
-// P3 for FMT_NARROW records (k <= 21, the default k; ordinary regions only -- skewed ones go to hot_list and the
-// generic folding kernel).  Same job as k_count_regions<FMT_NARROW, false>, with a compact LDS image and 32-bit keys:
-//   s_a[slot] = key31 | cnt << 32     key31 = the hash bits that region r does not imply: (top 32 hash bits - rstart[r])
-//                                     << 10 | the 10 hash bits below them (2k - log2 R <= 31 bits: R >= 2048, k <= 21);
-//                                     low word 0xFFFFFFFF = free.  cnt = instances (bit 31 = arrived as a tombstone).
-//   s_e[slot] = the eight u8 edge counters
-// 32 KiB per region instead of 48: four workgroups per CU; a probe reads the key AND the count in one word, the count
-// add returns the tier decision from the same word, and a record turns into its key with three 32-bit operations
-// (no 64-bit hash is rebuilt).  Per record: 2 LDS reads (two slots of the probe sequence) + 2 LDS atomics.
-constexpr uint32_t N32_EMPTY = 0xFFFFFFFFu, N32_TOMB = 1u << 31;
-#ifndef KQ_N32_OCC
-#define KQ_N32_OCC 6
-#endif
-// TIGHT: the sets hold FMT_TIGHT records (one u32 = key << 6 | edge indices, no lockstep byte).
-template <int KC, bool TIGHT>
-__global__ __launch_bounds__(P3_THREADS, KQ_N32_OCC) void k_count_regions_n32(TableView t, const P3Set* __restrict__ sets, uint32_t n_sets, int table_is_empty,
-                                                                      unsigned long long* __restrict__ hot_list, uint32_t rps) {
-    constexpr int PF = KQ_P3_PF;
-    constexpr uint32_t GRP = 64u * PF;
-    __shared__ uint64_t s_a[REGION_SLOTS];
-    __shared__ uint64_t s_e[REGION_SLOTS];
-    __shared__ uint64_t s_lut[64];
-    if (threadIdx.x < 64) s_lut[threadIdx.x] = idx6_to_pack(threadIdx.x);     // visible after the first region's barrier
-    __shared__ unsigned int s_new, s_kmers, s_grp;
-    constexpr int HC_LDS = 64;
-    __shared__ uint64_t s_hckey[HC_LDS];
-    __shared__ uint32_t s_hccnt[HC_LDS][8];
-    const int tid = threadIdx.x;
-    const uint32_t lane = tid & 63;
-    const uint32_t k = KC ? KC : t.k;
-    const uint32_t off_shift = 42 - 2 * k;                              // k <= 21
-    for (uint64_t r = t.reg_lo + blockIdx.x; r < t.reg_hi; r += gridDim.x) {
-        SetTickets<GRP> tk;
-        tk.build(sets, n_sets, r, lane);
-        uint64_t n_recs = tk.cnt;                                       // block-uniform after the reduction
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n_recs += __shfl_xor(n_recs, o, 64);
-        ulonglong2* gimg = reinterpret_cast<ulonglong2*>(t.slots + (r << REGION_SHIFT));
-        if (n_recs == 0) {
-            if (table_is_empty == 2)                                    // lazy kq_clear: this launch initialises every region
-                for (int i = tid; i < (int)REGION_SLOTS; i += P3_THREADS) gimg[i] = make_ulonglong2(0ull, 0ull);
-            continue;
-        }
-        if (n_recs > 32ull * REGION_SLOTS) {                            // skewed region: the folding kernel takes it
-            if (tid == 0) hot_list[1 + atomicAdd(&hot_list[0], 1ull)] = r;
-            continue;
-        }
-        const uint32_t bucket = (uint32_t)r / rps;
-        const uint32_t start_r = t.rstart[r];
-        const uint32_t top_base = (bucket << (32 - NARROW_CBITS)) - start_r;       // (top 32 hash bits of a record) - rstart[r] = top_base + (u32 >> 8)
-        const uint32_t start_lo = start_r << 10;                                   // TIGHT: key + start_lo = the low 32 bits of (top 32 bits | 10 below)
-        if (tid < HC_LDS) {
-            s_hckey[tid] = EMPTY_KEY;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s_hccnt[tid][e] = 0;
-        }
-        if (table_is_empty) {
-            for (int i = tid; i < (int)REGION_SLOTS; i += P3_THREADS) { s_a[i] = (uint64_t)N32_EMPTY; s_e[i] = 0; }
-        } else {
-            ulonglong2 v[REGION_SLOTS / P3_THREADS];
-#pragma unroll
-            for (int j = 0; j < (int)(REGION_SLOTS / P3_THREADS); ++j) v[j] = gimg[tid + j * P3_THREADS];
-#pragma unroll
-            for (int j = 0; j < (int)(REGION_SLOTS / P3_THREADS); ++j) {
-                const uint64_t w0 = v[j].x;                             // rem56 | cov8 << 56, rem = hash >> 8
-                uint64_t a = (uint64_t)N32_EMPTY;
-                if (w0) {
-                    const uint32_t key = (((uint32_t)(w0 >> 24) - start_r) << 10) | ((uint32_t)(w0 >> 14) & 1023u);
-                    const uint32_t c = (uint32_t)(w0 >> COV_SHIFT);
-                    a = (uint64_t)key | ((uint64_t)(c == COV8_TOMB ? (N32_TOMB | LOW_TIER_MAX) : c) << 32);
-                }
-                s_a[tid + j * P3_THREADS] = a;
-                s_e[tid + j * P3_THREADS] = v[j].y;
-            }
-        }
-        if (tid == 0) { s_new = 0; s_kmers = 0; s_grp = P3_THREADS / 64; }
-        __syncthreads();
-        uint32_t n_new = 0, n_ok = 0;
-        // hash of a key of this region (high-copy tier only)
-        auto hash_of = [&](uint32_t key) -> uint64_t { return ((uint64_t)(start_r + (key >> 10)) << 32) | ((uint64_t)(key & 1023u) << 22); };
-        auto add_wide = [&](uint32_t key31, uint64_t pack) {
-            const uint64_t h = hash_of(key31);
-            const uint64_t key = key_of_hash(h, t.k);
-            uint32_t e[8];
-#pragma unroll
-            for (int w = 0; w < 8; ++w) e[w] = (uint32_t)(pack >> (8 * w)) & 1u;
-            int hslot = -1;
-            uint32_t hp = (uint32_t)(h >> 40) & (HC_LDS - 1);
-            for (int probe = 0; probe < HC_LDS; ++probe, hp = (hp + 1) & (HC_LDS - 1)) {
-                uint64_t cur = __hip_atomic_load(&s_hckey[hp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (cur == EMPTY_KEY) cur = atomicCAS((unsigned long long*)&s_hckey[hp], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-                if (cur == EMPTY_KEY || cur == key) { hslot = (int)hp; break; }
-            }
-            if (hslot >= 0) {
-#pragma unroll
-                for (int w = 0; w < 8; ++w) if (e[w]) atomicAdd(&s_hccnt[hslot][w], e[w]);
-            } else {
-                hc_add(t, h, 0, 0, e);
-            }
-        };
-        // Records are double-buffered in registers (unconditional loads, index clamped); groups of GRP records are handed
-        // to waves from an LDS ticket, so waves that hit long probe chains take fewer groups.
-        uint32_t nxt_rec[PF], nxt_aux[PF];
-        uint32_t cur_n = 0;
-        auto fetch = [&](uint32_t g, uint32_t& n) {
-            uint32_t q, off, cnt; uint64_t lo_q;
-            tk.locate(g, q, off, cnt, lo_q);
-            const uint32_t* rp = reinterpret_cast<const uint32_t*>(sets[q].recs);
-            const uint8_t* ap = sets[q].aux;
-            n = min(cnt - off, GRP);
-#pragma unroll
-            for (int qq = 0; qq < PF; ++qq) {
-                const uint64_t j = lo_q + min(off + (uint32_t)qq * 64u + lane, cnt - 1u);
-                nxt_rec[qq] = ld_global(rp + j);
-                nxt_aux[qq] = TIGHT ? 0u : ld_global(ap + j);
-            }
-        };
-        uint32_t g_cur = tid >> 6;
-        fetch(g_cur, cur_n);
-        while (g_cur < tk.n_grp) {                                      // wave-uniform
-            uint32_t cur_rec[PF], cur_aux[PF];
-#pragma unroll
-            for (int q = 0; q < PF; ++q) { cur_rec[q] = nxt_rec[q]; cur_aux[q] = nxt_aux[q]; }
-            uint32_t g_nxt = 0;
-            if (lane == 0) g_nxt = atomicAdd(&s_grp, 1u);
-            g_nxt = __builtin_amdgcn_readfirstlane(g_nxt);
-            const uint32_t n_cur = cur_n;
-            fetch(g_nxt, cur_n);
-            g_cur = g_nxt;
-#pragma unroll
-            for (int q = 0; q < PF; ++q) {
-                const bool active = (uint32_t)q * 64u + lane < n_cur;
-                const uint32_t m = cur_rec[q], aux = cur_aux[q];
-                const uint32_t low = ((m & 0xFFu) << 2) | (aux & 3u);   // the 10 hash bits below the top 32
-                const uint32_t key = TIGHT ? m >> 6 : ((top_base + (m >> 8)) << 10) | low;
-                uint32_t pos = TIGHT ? (((key + start_lo) >> off_shift) & (REGION_SLOTS - 4))          // off_shift + 11 <= 32 (k >= 11); quad-aligned home (hash_offset)
-                             : KC == 21 ? (((m << 2) | (aux & 3u)) & (REGION_SLOTS - 4))
-                                        : (uint32_t)(((((uint64_t)bucket << 34) | ((uint64_t)m << 2) | (aux & 3u)) >> off_shift) & (REGION_SLOTS - 4));
-                const uint64_t pack = s_lut[TIGHT ? m & 63u : (aux >> 2) & 63u];
-                // find-or-claim: two slots of the probe sequence per LDS round trip; one CAS site
-                uint32_t slot = active ? REGION_SLOTS : 0u;             // REGION_SLOTS = still looking
-                uint32_t probes = 0;
-#ifdef KQ_ABL
-                if (KQ_ABL & 4) slot = active ? pos : 0u;               // ablation build (timing only, never shipped): no probe
-#endif
-                while (slot == REGION_SLOTS) {
-                    const uint32_t i0 = pos, i1 = (pos + 1) & (REGION_SLOTS - 1);
-                    const uint32_t c0 = (uint32_t)__hip_atomic_load(&s_a[i0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    const uint32_t c1 = (uint32_t)__hip_atomic_load(&s_a[i1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (c0 == key) { slot = i0; break; }
-                    const bool free0 = c0 == N32_EMPTY;
-                    if (!free0 && c1 == key) { slot = i1; break; }
-                    if (free0 || c1 == N32_EMPTY) {
-                        const uint32_t ic = free0 ? i0 : i1;
-                        const uint32_t got = (uint32_t)atomicCAS((unsigned long long*)&s_a[ic], (unsigned long long)N32_EMPTY, (unsigned long long)key);
-                        if (got == N32_EMPTY) { ++n_new; slot = ic; break; }
-                        if (got == key) { slot = ic; break; }
-                        continue;                                       // another key took it: look at the pair again
-                    }
-                    pos = (pos + 2) & (REGION_SLOTS - 1);
-                    if ((probes += 2) >= REGION_SLOTS) { atomicOr(&t.st->err_table_full, 1u); slot = REGION_SLOTS + 1; }
-                }
-                if (active && slot < REGION_SLOTS) {
-                    ++n_ok;
-#ifdef KQ_ABL
-                    const uint64_t old = (KQ_ABL & 2) ? 0 : atomicAdd((unsigned long long*)&s_a[slot], 1ull << 32);
-                    if (KQ_ABL & 1) continue;
-#else
-                    const uint64_t old = atomicAdd((unsigned long long*)&s_a[slot], 1ull << 32);
-#endif
-                    if (pack) {
-                        if ((uint32_t)(old >> 32) < LOW_TIER_MAX) atomicAdd((unsigned long long*)&s_e[slot], (unsigned long long)pack);
-                        else add_wide(key, pack);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { n_new += __shfl_down(n_new, o, 64); n_ok += __shfl_down(n_ok, o, 64); }
-        if (lane == 0) { if (n_new) atomicAdd(&s_new, n_new); if (n_ok) atomicAdd(&s_kmers, n_ok); }
-        __syncthreads();
-        if (tid < HC_LDS && s_hckey[tid] != EMPTY_KEY) {            // flush the region's high-copy sums: one entry per k-mer
-            HcSlot* hs = hc_upsert(t, s_hckey[tid]);
-            if (!hs) atomicOr(&t.st->err_hc_full, 1u);
-            else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) if (s_hccnt[tid][e]) atomicAdd((unsigned long long*)&hs->cnt[e], (unsigned long long)s_hccnt[tid][e]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < (int)(REGION_SLOTS / P3_THREADS); ++j) {
-            const int i = tid + j * P3_THREADS;
-            const uint64_t a = s_a[i];
-            ulonglong2 o = make_ulonglong2(0ull, 0ull);
-            if ((uint32_t)a != N32_EMPTY) {
-                const uint32_t key = (uint32_t)a, cw = (uint32_t)(a >> 32), c = cw & ~N32_TOMB;
-                uint64_t cov8 = (cw & N32_TOMB) ? COV8_TOMB : c;
-                if (c > LOW_TIER_MAX) { cov8 = COV8_TOMB; hc_add(t, hash_of(key), c - LOW_TIER_MAX, 0, nullptr); }
-                o = make_ulonglong2((((uint64_t)(start_r + (key >> 10))) << 24) | ((uint64_t)(key & 1023u) << 14) | (cov8 << COV_SHIFT), s_e[i]);
-            }
-            gimg[i] = o;
-        }
-        if (tid == 0) {
-            if (s_new) atomicAdd(&t.st->slots_used, (unsigned long long)s_new);
-            if (s_kmers) atomicAdd(&t.st->kmers_added, (unsigned long long)s_kmers);
-        }
-        __syncthreads();
-    }
-}
-
-
-// ---- k_count_regions_q4: the table pass for FMT_NARROW / FMT_TIGHT records, second formulation (round 3) ------------------
-// Same job and same HBM image as k_count_regions_n32; what changes is how a wave walks its records.  n32 sent every record
-// through a divergent find-or-claim loop: a wave paid the MAXIMUM probe count of its 64 lanes (4-6 iterations of ~20
-// instructions at load 0.65) for every group of 64 records, ~100 VALU + ~110 SALU per group -- the pass was bound by that
-// instruction stream, not by LDS or HBM (round-2 VERDICT, weak #4).  Here:
-//   * a k-mer's home is a 16-byte aligned QUAD of slots (hash_offset() is quad-aligned for every kernel of the library:
-//     the probe sequence is still linear, it just starts at a multiple of four), and the LDS image keeps the 32-bit keys in
-//     an array of their own, so ONE straight-line step reads the four keys of the home quad (two 8-byte LDS reads), finds the
-//     key or the first free slot of the quad, claims it with a single CAS if need be and applies the record: no loop, no
-//     per-lane iteration count.  ~88 % of the records end there (key in its home quad, or a free slot in it);
-//   * the rest go to a small per-wave queue in LDS and are drained 64 at a time by the loop formulation -- which then runs
-//     with every lane busy on a record that needs it, instead of 64 lanes waiting for the slowest one.
-//   s_key[slot]  = key31 (the hash bits region r does not imply, as in n32) or N32_EMPTY
-//   s_cnt[slot]  = instances (bit 31 = arrived as a tombstone)
+// ---- k_count_regions_q4: the table pass for FMT_NARROW / FMT_TIGHT records (k <= 21, the default k) -----------------------
+// Ordinary regions only: skewed ones go to hot_list and the generic folding kernel.  Same job and same HBM image as
+// k_count_regions<FMT_NARROW, false>, with a compact LDS image and 32-bit keys:
+//   s_key[slot]  = key31 = the hash bits that region r does not imply: (top 32 hash bits - rstart[r]) << 10 | the 10 hash
+//                  bits below them (2k - log2 R <= 31 bits: R >= 2048, k <= 21), or Q4_EMPTY (0xFFFFFFFF) = free
+//   s_cnt[slot]  = instances (Q4_TOMB, bit 31 = arrived as a tombstone)
 //   s_e[slot]    = the eight u8 edge counters
+// 32 KiB per region instead of 48: four workgroups per CU, and a record turns into its key with three 32-bit operations
+// (no 64-bit hash is rebuilt).
+// How a wave walks its records.  A divergent find-or-claim loop per record makes a wave pay the MAXIMUM probe count of its 64
+// lanes (4-6 iterations of ~20 instructions at load 0.65) for every group of 64 records, ~100 VALU + ~110 SALU per group: a
+// pass in that form (round 2, 573 us on configs[1]) was bound by that instruction stream, not by LDS or HBM.  So:
+//   * a k-mer's home is a 16-byte aligned QUAD of slots (hash_offset() is quad-aligned for every kernel of the library:
+//     the probe sequence is still linear, it just starts at a multiple of four), and the keys lie in an array of their own,
+//     so ONE straight-line step reads the four keys of the home quad (two 8-byte LDS reads), finds the key or the first
+//     free slot of the quad, claims it with a single CAS if need be and applies the record: no loop, no per-lane
+//     iteration count.  ~88 % of the records end there (key in its home quad, or a free slot in it);
+//   * the rest go to a small per-wave queue in LDS and are drained 64 at a time by a probe loop -- which then runs with
+//     every lane busy on a record that needs it, instead of 64 lanes waiting for the slowest one.
+// One ticket per wave is in flight; two were measured (38 spilled registers): 3 Gbp 74.8 -> 85.1 ms per step, with two
+// records per lane 78.8.
+constexpr uint32_t Q4_EMPTY = 0xFFFFFFFFu, Q4_TOMB = 1u << 31;
 #ifndef KQ_Q4_QCAP
 #define KQ_Q4_QCAP 128
-#endif
-#ifndef KQ_Q4_DEPTH
-#define KQ_Q4_DEPTH 1          // tickets a wave has in flight, 4-byte records: 2 was measured (38 spilled registers): 3 Gbp 74.8 -> 85.1 ms per step, with two records per lane 78.8
-#endif
-#ifndef KQ_Q4_DEPTH_NT
-#define KQ_Q4_DEPTH_NT 1       // 5-byte records (small tables: few sets, long pieces)
 #endif
 #ifndef KQ_Q4_PF_TIGHT
 #define KQ_Q4_PF_TIGHT 4       // records per lane and ticket for 4-byte records (one register each): 1000 Mbp 20.2 -> 18.7 ms per step against 2; 5-byte records keep 2 (35 spilled registers at 4, no gain)
@@ -1283,7 +1073,6 @@ template <int KC, bool TIGHT>
 __global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(TableView t, const P3Set* __restrict__ sets, uint32_t n_sets, int table_is_empty,
                                                                      unsigned long long* __restrict__ hot_list, uint32_t rps) {
     constexpr int PF = TIGHT ? KQ_Q4_PF_TIGHT : KQ_P3_PF;
-    constexpr int DEPTH = TIGHT ? KQ_Q4_DEPTH : KQ_Q4_DEPTH_NT;            // tickets a wave has in flight
     constexpr uint32_t GRP = 64u * PF;
     constexpr uint32_t QCAP = KQ_Q4_QCAP, NONE = 0xFFFFFFFFu;
     __shared__ uint64_t s_key2[REGION_SLOTS / 2];                       // the keys, read two at a time
@@ -1294,40 +1083,21 @@ __global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(Tabl
     uint32_t* s_key = reinterpret_cast<uint32_t*>(s_key2);
     if (threadIdx.x < 64) s_lut[threadIdx.x] = idx6_to_pack(threadIdx.x);     // visible after the first region's barrier
     __shared__ unsigned int s_new, s_kmers, s_grp;
-    constexpr int HC_LDS = 64;
-    __shared__ uint64_t s_hckey[HC_LDS];
+    __shared__ uint64_t s_hckey[HC_LDS];                                // high-copy tier of this region (hc_lds_*)
     __shared__ uint32_t s_hccnt[HC_LDS][8];
     const int tid = threadIdx.x;
     const uint32_t lane = tid & 63, wave = tid >> 6;
     const uint32_t k = KC ? KC : t.k;
     const uint32_t off_shift = 42 - 2 * k;                              // k <= 21
-#ifdef KQ_STAMPS
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-#endif
     for (uint64_t r = t.reg_lo + blockIdx.x; r < t.reg_hi; r += gridDim.x) {
         SetTickets<GRP> tk;
-        tk.build(sets, n_sets, r, lane);
-        uint64_t n_recs = tk.cnt;                                       // block-uniform after the reduction
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n_recs += __shfl_xor(n_recs, o, 64);
+        if (!region_gate<Q4_THREADS, false>(tk, t, sets, n_sets, r, table_is_empty, hot_list)) continue;
         ulonglong2* gimg = reinterpret_cast<ulonglong2*>(t.slots + (r << REGION_SHIFT));
-        if (n_recs == 0) {
-            if (table_is_empty == 2)                                    // lazy kq_clear: this launch initialises every region
-                for (int i = tid; i < (int)REGION_SLOTS; i += Q4_THREADS) gimg[i] = make_ulonglong2(0ull, 0ull);
-            continue;
-        }
-        if (n_recs > 32ull * REGION_SLOTS) {                            // skewed region: the folding kernel takes it
-            if (tid == 0) hot_list[1 + atomicAdd(&hot_list[0], 1ull)] = r;
-            continue;
-        }
         // the first records of this wave are requested NOW: their latency (an HBM round trip behind the ticket build's two)
         // runs under the image set-up and the barrier instead of behind them (round 3: a region visit is mostly such
         // dependent round trips -- 23 ns per region and pass at 5.3 M regions whatever the number of records)
-        // (DEPTH = 2 keeps two tickets per wave in flight: a region's records come as one short piece per pending set, ~170
-        // records of each of 30 sets at 3 Gbp, every piece from another place of the arena.  Measured and not the default.)
-        constexpr int NW = Q4_THREADS / 64;
-        uint32_t recA[PF], auxA[PF], recB[PF], auxB[PF];
-        uint32_t nA = 0, nB = 0;
+        uint32_t recA[PF], auxA[PF];
+        uint32_t nA = 0;
         auto fetch = [&](uint32_t g, uint32_t (&rec)[PF], uint32_t (&aux)[PF], uint32_t& n) {
             uint32_t q, off, cnt; uint64_t lo_q;
             tk.locate(g, q, off, cnt, lo_q);
@@ -1341,21 +1111,15 @@ __global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(Tabl
                 aux[qq] = TIGHT ? 0u : ld_global(ap + j);
             }
         };
-        KQ_STAMP(0);                                                    // kernel start -> ticket build + reduction done
-        uint32_t gA = wave, gB = wave + NW;                              // the first two tickets of a wave are its own; the rest come from s_grp
+        uint32_t gA = wave;                                             // the first ticket of a wave is its own; the rest come from s_grp
         fetch(gA, recA, auxA, nA);
-        if (DEPTH == 2) fetch(gB, recB, auxB, nB);
         const uint32_t bucket = (uint32_t)r / rps;
         const uint32_t start_r = t.rstart[r];
         const uint32_t top_base = (bucket << (32 - NARROW_CBITS)) - start_r;       // (top 32 hash bits of a 5-byte record) - rstart[r] = top_base + (u32 >> 8)
         const uint32_t start_lo = start_r << 10;                                   // key + start_lo = the low 32 bits of (top 32 hash bits | the 10 below)
-        if (tid < HC_LDS) {
-            s_hckey[tid] = EMPTY_KEY;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s_hccnt[tid][e] = 0;
-        }
+        hc_lds_reset(s_hckey, s_hccnt);
         if (table_is_empty) {
-            for (int i = tid; i < (int)REGION_SLOTS; i += Q4_THREADS) { s_key[i] = N32_EMPTY; s_cnt[i] = 0; s_e[i] = 0; }
+            for (int i = tid; i < (int)REGION_SLOTS; i += Q4_THREADS) { s_key[i] = Q4_EMPTY; s_cnt[i] = 0; s_e[i] = 0; }
         } else {
             ulonglong2 v[REGION_SLOTS / Q4_THREADS];
 #pragma unroll
@@ -1363,41 +1127,26 @@ __global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(Tabl
 #pragma unroll
             for (int j = 0; j < (int)(REGION_SLOTS / Q4_THREADS); ++j) {
                 const uint64_t w0 = v[j].x;                             // rem56 | cov8 << 56, rem = hash >> 8
-                uint32_t key = N32_EMPTY, cnt = 0;
+                uint32_t key = Q4_EMPTY, cnt = 0;
                 if (w0) {
                     key = (((uint32_t)(w0 >> 24) - start_r) << 10) | ((uint32_t)(w0 >> 14) & 1023u);
                     const uint32_t c = (uint32_t)(w0 >> COV_SHIFT);
-                    cnt = c == COV8_TOMB ? (N32_TOMB | LOW_TIER_MAX) : c;
+                    cnt = c == COV8_TOMB ? (Q4_TOMB | LOW_TIER_MAX) : c;
                 }
                 s_key[tid + j * Q4_THREADS] = key;
                 s_cnt[tid + j * Q4_THREADS] = cnt;
                 s_e[tid + j * Q4_THREADS] = v[j].y;
             }
         }
-        if (tid == 0) { s_new = 0; s_kmers = 0; s_grp = DEPTH * (Q4_THREADS / 64); }
+        if (tid == 0) { s_new = 0; s_kmers = 0; s_grp = Q4_THREADS / 64; }
         __syncthreads();
-        KQ_STAMP(1);                                                    // first fetch issued, image init / load, barrier
         uint32_t n_new = 0, n_ok = 0;
         auto hash_of = [&](uint32_t key) -> uint64_t { return ((uint64_t)(start_r + (key >> 10)) << 32) | ((uint64_t)(key & 1023u) << 22); };
         auto add_wide = [&](uint32_t key31, uint64_t pack) {            // an edge of a k-mer beyond 254 instances: the region's LDS high-copy sums
-            const uint64_t h = hash_of(key31);
-            const uint64_t key = key_of_hash(h, t.k);
             uint32_t e[8];
 #pragma unroll
             for (int w = 0; w < 8; ++w) e[w] = (uint32_t)(pack >> (8 * w)) & 1u;
-            int hslot = -1;
-            uint32_t hp = (uint32_t)(h >> 40) & (HC_LDS - 1);
-            for (int probe = 0; probe < HC_LDS; ++probe, hp = (hp + 1) & (HC_LDS - 1)) {
-                uint64_t cur = __hip_atomic_load(&s_hckey[hp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (cur == EMPTY_KEY) cur = atomicCAS((unsigned long long*)&s_hckey[hp], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-                if (cur == EMPTY_KEY || cur == key) { hslot = (int)hp; break; }
-            }
-            if (hslot >= 0) {
-#pragma unroll
-                for (int w = 0; w < 8; ++w) if (e[w]) atomicAdd(&s_hccnt[hslot][w], e[w]);
-            } else {
-                hc_add(t, h, 0, 0, e);
-            }
+            hc_lds_add(t, s_hckey, s_hccnt, hash_of(key31), e);
         };
         // one instance of the k-mer in `slot`
         auto apply = [&](uint32_t slot, uint32_t key, uint64_t pack) {
@@ -1420,13 +1169,13 @@ __global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(Tabl
             off = k0 == key ? 0u : off;
             full = false;
             if (off < 4u) return pos + off;
-            uint32_t eo = k3 == N32_EMPTY ? 3u : 4u;
-            eo = k2 == N32_EMPTY ? 2u : eo;
-            eo = k1 == N32_EMPTY ? 1u : eo;
-            eo = k0 == N32_EMPTY ? 0u : eo;
+            uint32_t eo = k3 == Q4_EMPTY ? 3u : 4u;
+            eo = k2 == Q4_EMPTY ? 2u : eo;
+            eo = k1 == Q4_EMPTY ? 1u : eo;
+            eo = k0 == Q4_EMPTY ? 0u : eo;
             if (eo == 4u) { full = true; return NONE; }
-            const uint32_t got = atomicCAS(&s_key[pos + eo], N32_EMPTY, key);
-            if (got == N32_EMPTY) { ++n_new; return pos + eo; }
+            const uint32_t got = atomicCAS(&s_key[pos + eo], Q4_EMPTY, key);
+            if (got == Q4_EMPTY) { ++n_new; return pos + eo; }
             return got == key ? pos + eo : NONE;
         };
         // home quad of a key: the low 32 bits of (top 32 hash bits | the 10 below) are key + start_lo; k < 11 (a key space
@@ -1487,61 +1236,34 @@ __global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(Tabl
                 }
             }
         };
-        // tickets are handed out in increasing order and a wave looks at A, B, A, B ...: the first ticket past the end ends its walk
-        for (;;) {                                                      // wave-uniform
-            if (gA >= tk.n_grp) break;
-            {
-                uint32_t cur_rec[PF], cur_aux[PF];
+        // tickets are handed out in increasing order: the first one past the end ends a wave's walk
+        while (gA < tk.n_grp) {                                         // wave-uniform
+            uint32_t cur_rec[PF], cur_aux[PF];
 #pragma unroll
-                for (int q = 0; q < PF; ++q) { cur_rec[q] = recA[q]; cur_aux[q] = auxA[q]; }
-                const uint32_t n_cur = nA;
-                gA = grab();
-                fetch(gA, recA, auxA, nA);
-                process(cur_rec, cur_aux, n_cur);
-            }
-            if (DEPTH == 2) {
-                if (gB >= tk.n_grp) break;
-                uint32_t cur_rec[PF], cur_aux[PF];
-#pragma unroll
-                for (int q = 0; q < PF; ++q) { cur_rec[q] = recB[q]; cur_aux[q] = auxB[q]; }
-                const uint32_t n_cur = nB;
-                gB = grab();
-                fetch(gB, recB, auxB, nB);
-                process(cur_rec, cur_aux, n_cur);
-            }
+            for (int q = 0; q < PF; ++q) { cur_rec[q] = recA[q]; cur_aux[q] = auxA[q]; }
+            const uint32_t n_cur = nA;
+            gA = grab();
+            fetch(gA, recA, auxA, nA);
+            process(cur_rec, cur_aux, n_cur);
         }
         drain();
-        KQ_STAMP(2);                                                    // record walk (wave 0)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { n_new += __shfl_down(n_new, o, 64); n_ok += __shfl_down(n_ok, o, 64); }
-        if (lane == 0) { if (n_new) atomicAdd(&s_new, n_new); if (n_ok) atomicAdd(&s_kmers, n_ok); }
+        region_totals_wave(n_new, n_ok, s_new, s_kmers);
         __syncthreads();
-        if (tid < HC_LDS && s_hckey[tid] != EMPTY_KEY) {            // flush the region's high-copy sums: one entry per k-mer
-            HcSlot* hs = hc_upsert(t, s_hckey[tid]);
-            if (!hs) atomicOr(&t.st->err_hc_full, 1u);
-            else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) if (s_hccnt[tid][e]) atomicAdd((unsigned long long*)&hs->cnt[e], (unsigned long long)s_hccnt[tid][e]);
-            }
-        }
+        hc_lds_flush(t, s_hckey, s_hccnt);
 #pragma unroll
         for (int j = 0; j < (int)(REGION_SLOTS / Q4_THREADS); ++j) {
             const int i = tid + j * Q4_THREADS;
             const uint32_t key = s_key[i];
             ulonglong2 o = make_ulonglong2(0ull, 0ull);
-            if (key != N32_EMPTY) {
-                const uint32_t cw = s_cnt[i], c = cw & ~N32_TOMB;
-                uint64_t cov8 = (cw & N32_TOMB) ? COV8_TOMB : c;
+            if (key != Q4_EMPTY) {
+                const uint32_t cw = s_cnt[i], c = cw & ~Q4_TOMB;
+                uint64_t cov8 = (cw & Q4_TOMB) ? COV8_TOMB : c;
                 if (c > LOW_TIER_MAX) { cov8 = COV8_TOMB; hc_add(t, hash_of(key), c - LOW_TIER_MAX, 0, nullptr); }
                 o = make_ulonglong2((((uint64_t)(start_r + (key >> 10))) << 24) | ((uint64_t)(key & 1023u) << 14) | (cov8 << COV_SHIFT), s_e[i]);
             }
             gimg[i] = o;
         }
-        KQ_STAMP(3);                                                    // barrier (slowest wave), high-copy flush, image store (waited for)
-        if (tid == 0) {
-            if (s_new) atomicAdd(&t.st->slots_used, (unsigned long long)s_new);
-            if (s_kmers) atomicAdd(&t.st->kmers_added, (unsigned long long)s_kmers);
-        }
+        region_totals_store(t, s_new, s_kmers);
         __syncthreads();
     }
 }

@@ -133,7 +133,7 @@ constexpr int FMT_TOP8 = 4;
 // FMT_TIGHT (k <= 21, tables of >= 2^16 regions; the LAST level's output and the pending sets of the count path only): one
 // u32, no lockstep byte.  A record that has reached its region r needs only the hash bits r does not imply:
 //   (top 32 hash bits - rstart[r]) << 16 | the 10 hash bits below << 6 | the two edge indices
-// (ceil(2^32 / R) <= 2^16 values of the first field).  `>> 6` is the 32-bit key of k_count_regions_n32.  4 bytes instead of
+// (ceil(2^32 / R) <= 2^16 values of the first field).  `>> 6` is the 32-bit key of k_count_regions_q4.  4 bytes instead of
 // 5 in the arena, one store per record instead of two in the last level, one load in the table pass.
 constexpr int FMT_TIGHT = 5;
 constexpr int FMT_NARROW_TO_TIGHT = 6;      // k_lv_scatter only: narrow records in, tight records out (last level)
@@ -184,18 +184,7 @@ struct MsShared {
     uint32_t loff[NBC];
     uint32_t gbase[NBC];                     // output cursors: a partition pass handles < 2^32 records (host-checked)
     uint32_t wave_sum[16];
-#ifdef KQ_MS_STAMPS
-    unsigned long long stamp_last;
-    int stamp_on;
-#endif
 };
-#ifdef KQ_MS_STAMPS   // diagnostic build only (never shipped): per-phase cycle sums of the multisplit rounds
-__device__ unsigned long long g_ms_stamps[16];
-#define KQ_MS_STAMP(s, i) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); \
-        __builtin_amdgcn_sched_barrier(0); if (threadIdx.x == 0 && (s).stamp_on) { atomicAdd(&g_ms_stamps[i], t_ - (s).stamp_last); (s).stamp_last = t_; } } while (0)
-#else
-#define KQ_MS_STAMP(s, i) do { } while (0)
-#endif
 
 // exclusive scan of s.hist[0..nb) into s.loff.  nb <= NBC.
 template <int THREADS, class S>
@@ -243,10 +232,8 @@ __device__ __forceinline__ void block_multisplit(S& s, const uint64_t (&rec)[ITE
                                                  uint64_t* __restrict__ out, uint8_t* __restrict__ out_aux, F pre_store = F(), uint32_t rs = 0) {
     const int tid = threadIdx.x;
     const uint32_t sub = (uint32_t)tid & ((1u << rs) - 1u), n_ctr = (nb + 1) << rs;
-    KQ_MS_STAMP(s, 0);                            // caller: loads landed, bins computed
     for (uint32_t b = tid; b < n_ctr; b += THREADS) s.hist[b] = 0;
     __syncthreads();
-    KQ_MS_STAMP(s, 1);                            // zero hist + barrier
     static_assert(THREADS * ITEMS <= S::tile, "round size");
     // FMT_NARROW: rec[i] is the staged word itself (u32 | bin << 32 | byte << 48, narrow_word()); aux[] and
     // bin[] are not read, which saves the caller 2 x ITEMS registers
@@ -260,9 +247,7 @@ __device__ __forceinline__ void block_multisplit(S& s, const uint64_t (&rec)[ITE
         if (b != nb) rank[i] = atomicAdd(&s.hist[(b << rs) | sub], 1u);
     }
     __syncthreads();
-    KQ_MS_STAMP(s, 2);                            // rank atomics + barrier
     ms_scan<THREADS>(s, n_ctr);
-    KQ_MS_STAMP(s, 3);                            // scan (2 barriers)
     // from here to the end of the round gbase[b] is relative to the staged order: the output index of the
     // staged record j of bin b is gbase[b] + j (one LDS read per record in the copy-out instead of two)
     for (uint32_t b = tid; b < nb; b += THREADS) s.gbase[b] -= s.loff[b << rs];
@@ -280,7 +265,6 @@ __device__ __forceinline__ void block_multisplit(S& s, const uint64_t (&rec)[ITE
         }
     }
     __syncthreads();
-    KQ_MS_STAMP(s, 4);                            // stage writes + barrier
     const uint32_t total = s.loff[nb << rs];     // records in front of the discard bin
     // fully unrolled so that the LDS reads of all ITEMS positions are in flight together (a rolled
     // loop is a chain of three dependent LDS round trips per record)
@@ -296,21 +280,13 @@ __device__ __forceinline__ void block_multisplit(S& s, const uint64_t (&rec)[ITE
     }
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) cg[it] = s.gbase[cb[it]] + (tid + it * THREADS);
-    KQ_MS_STAMP(s, 5);                            // copy-out LDS reads
     pre_store();
-    KQ_MS_STAMP(s, 6);                            // prefetch landed
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const uint32_t j = tid + it * THREADS;
         if (j < total) {
             if (FMT == FMT_NARROW) {
-#ifdef KQ_EXP_NOSTORE      // timing experiment only (results are wrong): how much of a scatter's time its global stores are
-                if (KQ_EXP_NOSTORE >= 2) continue;
-#endif
                 reinterpret_cast<uint32_t*>(out)[cg[it]] = (uint32_t)cv[it];
-#ifdef KQ_EXP_NOSTORE
-                continue;
-#endif
                 if (out_aux) out_aux[cg[it]] = (uint8_t)(cv[it] >> 48);       // (uniform) FMT_TIGHT output has no lockstep byte
             } else {
                 out[cg[it]] = cv[it];
@@ -319,7 +295,6 @@ __device__ __forceinline__ void block_multisplit(S& s, const uint64_t (&rec)[ITE
         }
     }
     __syncthreads();
-    KQ_MS_STAMP(s, 7);                            // global stores issued + barrier
     // advance the cursors: gbase[b] + loff[first counter of bin b] is the absolute cursor, the bin's count of this round is
     // the distance to the first counter of the next bin
     for (uint32_t b = tid; b < nb; b += THREADS) s.gbase[b] += s.loff[(b + 1) << rs];     // (loff is next written behind the next round's barriers)

@@ -827,26 +827,28 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     // its address and content between the passes).  The first pass that scans a slice counts for all n ranges in one histogram
     // launch (bin = range * 256 + bucket: the block of a range is contiguous in the bin-major matrix) and keeps the raw counts;
     // every pass takes its block from there -- (n - 1) of the n histogram scans of a slice are never run.
+    // the cached count matrix of `key`, or a fresh one of `bytes` bytes that `launch` fills; null: no room (4 GiB cap, hipMalloc)
+    auto cached_hist = [&](const kq_handle::HistKey& key, size_t bytes, auto launch) -> kq_handle::HistEntry* {
+        for (auto& e : h->hist_cache) if (e.key == key) return &e;
+        if (h->hist_cache_bytes + bytes > ((size_t)4 << 30)) return nullptr;
+        unsigned long long* buf = nullptr;
+        if (hipMalloc((void**)&buf, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        launch(buf);
+        h->hist_cache.push_back(kq_handle::HistEntry{key, buf, bytes});
+        h->hist_cache_bytes += bytes;
+        return &h->hist_cache.back();
+    };
     bool have_hist = false;
+    const size_t row = (size_t)p->g1 * sizeof(unsigned long long), block = row << NARROW_CBITS;       // one bucket's counts; the matrix of one range
     if (narrow_filt && h->map_passes > 1 && P1_F == 1 && !h->hist_cache_off) {
         const uint32_t n = (uint32_t)h->map_passes, per = cfg.map_count / n, rr = cfg.filt_lo / per;
         if (cfg.filt_lo == rr * per && cfg.filt_hi == (rr + 1) * per) {
-            const kq_handle::HistKey key{ab, pinv, lead, len, er.lo, er.hi, p->g1, n, h->k};
-            const size_t block = (size_t)(1u << NARROW_CBITS) * p->g1 * sizeof(unsigned long long);
-            kq_handle::HistEntry* ent = nullptr;
-            for (auto& e : h->hist_cache) if (e.key == key) { ent = &e; break; }
-            if (!ent && h->hist_cache_bytes + n * block <= ((size_t)4 << 30)) {
-                unsigned long long* buf = nullptr;
-                if (hipMalloc((void**)&buf, n * block) == hipSuccess) {
-                    PartCfg all = cfg;
-                    all.n_rng = n; all.n_coarse = n << NARROW_CBITS;
-                    if (h->k == 21) hipLaunchKernelGGL((k_p1_hist<5, 21>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
-                    else hipLaunchKernelGGL((k_p1_hist<5, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
-                    h->hist_cache.push_back(kq_handle::HistEntry{key, buf, n * block});
-                    h->hist_cache_bytes += n * block;
-                    ent = &h->hist_cache.back();
-                } else (void)hipGetLastError();
-            }
+            const auto* ent = cached_hist({ab, pinv, lead, len, er.lo, er.hi, p->g1, n, h->k}, n * block, [&](unsigned long long* buf) {
+                PartCfg all = cfg;
+                all.n_rng = n; all.n_coarse = n << NARROW_CBITS;
+                if (h->k == 21) hipLaunchKernelGGL((k_p1_hist<5, 21>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
+                else hipLaunchKernelGGL((k_p1_hist<5, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
+            });
             if (ent) {
                 (void)hipMemcpyAsync(p->m1, (const char*)ent->m1_all + rr * block, block, hipMemcpyDeviceToDevice, h->stream);
                 have_hist = true;
@@ -856,22 +858,12 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     // the same for bucket-range passes (windowed table): the unfiltered bucket matrix serves every window -- the rows of the
     // other buckets are zeroed before the scan
     if (narrow_win && h->map_passes > 1 && P1_F == 1 && !h->hist_cache_off) {
-        const kq_handle::HistKey key{ab, pinv, lead, len, er.lo, er.hi, p->g1, 0xB0C4E7u, h->k};
-        const size_t block = (size_t)(1u << NARROW_CBITS) * p->g1 * sizeof(unsigned long long), row = (size_t)p->g1 * sizeof(unsigned long long);
-        kq_handle::HistEntry* ent = nullptr;
-        for (auto& e : h->hist_cache) if (e.key == key) { ent = &e; break; }
-        if (!ent && h->hist_cache_bytes + block <= ((size_t)4 << 30)) {
-            unsigned long long* buf = nullptr;
-            if (hipMalloc((void**)&buf, block) == hipSuccess) {
-                PartCfg all = cfg;
-                all.win_lo = 0; all.win_hi = 1u << NARROW_CBITS;
-                if (h->k == 21) hipLaunchKernelGGL((k_p1_hist<2, 21>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
-                else hipLaunchKernelGGL((k_p1_hist<2, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
-                h->hist_cache.push_back(kq_handle::HistEntry{key, buf, block});
-                h->hist_cache_bytes += block;
-                ent = &h->hist_cache.back();
-            } else (void)hipGetLastError();
-        }
+        const auto* ent = cached_hist({ab, pinv, lead, len, er.lo, er.hi, p->g1, 0xB0C4E7u, h->k}, block, [&](unsigned long long* buf) {
+            PartCfg all = cfg;
+            all.win_lo = 0; all.win_hi = 1u << NARROW_CBITS;
+            if (h->k == 21) hipLaunchKernelGGL((k_p1_hist<2, 21>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
+            else hipLaunchKernelGGL((k_p1_hist<2, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
+        });
         if (ent) {
             (void)hipMemcpyAsync(p->m1, ent->m1_all, block, hipMemcpyDeviceToDevice, h->stream);
             if (cfg.win_lo) (void)hipMemsetAsync(p->m1, 0, (size_t)cfg.win_lo * row, h->stream);
@@ -986,13 +978,7 @@ static LevelCfg level_narrow(const PartCfg& cfg, uint32_t sub_bits = 0, bool mid
 // records grouped by region and p->group_base their offsets
 static void run_narrow_levels(kq_handle* h, PartPlan* p, const uint64_t** sorted, const uint8_t** sorted_aux, const P3Set* dst = nullptr, bool tight = false);
 // FMT_TIGHT output of the last split level (count path only: the lookup kernels read 5-byte records)
-static bool tight_ok(const kq_handle* h, const PartPlan& p) {
-#ifdef KQ_NO_TIGHT
-    (void)h; (void)p; return false;
-#else
-    return p.fmt == FMT_NARROW && p.R >= TIGHT_MIN_REGIONS && h->rstart != nullptr;
-#endif
-}
+static bool tight_ok(const kq_handle* h, const PartPlan& p) { return p.fmt == FMT_NARROW && p.R >= TIGHT_MIN_REGIONS && h->rstart != nullptr; }
 static LevelCfg level_flat_to_coarse(const PartCfg& cfg) {
     LevelCfg lv; lv.n_regions = cfg.n_regions; lv.n_seg = 1; lv.nb = cfg.n_coarse; lv.seg_shift = 32; lv.out_shift = cfg.g_shift; lv.in_raw = 0; lv.k = 0; lv.narrow = 0; lv.top8 = 0;
     lv.nr_shift = lv.nr_rps = lv.nr_sub = lv.nr_inv = 0; lv.nr_div = 1;
@@ -1112,28 +1098,23 @@ static int flush_pending_base(kq_handle* h) {
     const int empty = h->slots_dirty ? 2 : h->table_empty ? 1 : 0;
     const int fmt = h->pend_fmt;
     const uint32_t rps = (fmt == FMT_NARROW || fmt == FMT_TIGHT || fmt == FMT_TOP8) ? (uint32_t)(R >> NARROW_CBITS) : 1u;
+#define KQ_HOT(F) hipLaunchKernelGGL((k_count_regions<F, true>), grid_hot, block, 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps)
 #define KQ_P3(F) do { \
         hipLaunchKernelGGL((k_count_regions<F, false>), grid, block, 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps); \
-        hipLaunchKernelGGL((k_count_regions<F, true>), grid_hot, block, 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps); } while (0)
-#ifdef KQ_NO_N32
-    if (fmt == FMT_NARROW || fmt == FMT_TIGHT) KQ_P3(FMT_NARROW); else      // (pend_aux_fmt == AUX_TIGHT tells the generic kernel about FMT_TIGHT sets)
-#endif
-    if (fmt == FMT_NARROW || fmt == FMT_TIGHT) {
-        // ordinary regions: the compact 32-bit-key kernel; skewed ones: the generic folding kernel
-#ifdef KQ_P3_V1       // A/B build: round 2's loop formulation
-#define KQ_N32(KC, T) hipLaunchKernelGGL((k_count_regions_n32<KC, T>), grid, block, 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, empty, hot, rps)
-#else
-#define KQ_N32(KC, T) hipLaunchKernelGGL((k_count_regions_q4<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, empty, hot, rps)
-#endif
-        if (fmt == FMT_TIGHT) { if (h->k == 21) KQ_N32(21, true); else KQ_N32(0, true); }
-        else                  { if (h->k == 21) KQ_N32(21, false); else KQ_N32(0, false); }
-#undef KQ_N32
-        hipLaunchKernelGGL((k_count_regions<FMT_NARROW, true>), grid_hot, block, 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps);
-    }
+        KQ_HOT(F); } while (0)
+#define KQ_Q4(KC, T) do { \
+        hipLaunchKernelGGL((k_count_regions_q4<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, empty, hot, rps); \
+        KQ_HOT(FMT_NARROW); } while (0)
+    // ordinary regions of 4- and 5-byte records: the compact 32-bit-key kernel; skewed ones: the generic folding kernel
+    // (pend_aux_fmt == AUX_TIGHT tells it about FMT_TIGHT sets)
+    if (fmt == FMT_TIGHT)       { if (h->k == 21) KQ_Q4(21, true); else KQ_Q4(0, true); }
+    else if (fmt == FMT_NARROW) { if (h->k == 21) KQ_Q4(21, false); else KQ_Q4(0, false); }
     else if (fmt == FMT_TOP8) KQ_P3(FMT_TOP8);
     else if (fmt == FMT_WIDE) KQ_P3(FMT_WIDE);
     else KQ_P3(FMT_PACK8);
+#undef KQ_Q4
 #undef KQ_P3
+#undef KQ_HOT
     h->n_pend = 0; h->arena_used = 0; h->pend_records = 0;
     ++h->table_passes;
     // only now (every failure path of the partition stages lies before this point): the table has content, and a lazily
