@@ -335,6 +335,9 @@ struct GpuSink {
     std::mutex m;
     std::condition_variable cv;
     bool failed = false;                          // a parser thread or a submit has failed: nobody waits for a buffer any more (under m)
+    std::string cause;                            // what failed first (under m, set with `failed`): the threads that give up because of it
+                                                  // throw the same text, so the error reported does not depend on which thread's exception is seen first
+    void set_failed(const std::string& why) { if (!failed) { failed = true; cause = why; } }     // (call under m)
     std::atomic<long long> ns_wait{0}, ns_pack{0}, ns_call{0}, n_submit{0}, n_dev_submit{0};     // KQ_INGEST_TRACE: where the threads spend their time
     GpuSink(kq_handle* handle, unsigned n_buffers, size_t buffer_bytes, bool pack, bool dev_parse = false)
         : h(handle), cap(buffer_bytes), packed(pack && !dev_parse), device_parse(dev_parse), pool(n_buffers) {
@@ -354,7 +357,7 @@ struct GpuSink {
         { std::lock_guard<std::mutex> l(m); for (int i : flying) tickets.push_back(pool[i].ticket); for (int i : flying) free_list.push_back(i); flying.clear(); }
         for (uint64_t tk : tickets) (void)kq_host_wait(h, tk);
     }
-    void fail() { { std::lock_guard<std::mutex> l(m); failed = true; } cv.notify_all(); }
+    void fail(const std::string& why = "") { { std::lock_guard<std::mutex> l(m); set_failed(why); } cv.notify_all(); }
     ~GpuSink() {
         drain();
         for (auto& b : pool) { if (packed) free(b.ascii); else kq_host_free(b.ascii); kq_host_free(b.codes); kq_host_free(b.inv); }
@@ -377,7 +380,7 @@ struct GpuSink {
             // back to the pool; on failure every thread waiting for a buffer is woken and throws (they used to
             // wait forever for buffers held by threads that had died)
             const std::string err = injected ? "submit failed (injected by KQ_TEST_FAIL_SUBMIT)" : rc != KQ_OK ? kq_last_error() : "";
-            { std::lock_guard<std::mutex> l(m); free_list.push_back(i); if (rc != KQ_OK) failed = true; }
+            { std::lock_guard<std::mutex> l(m); free_list.push_back(i); if (rc != KQ_OK) set_failed("Error: " + err); }
             cv.notify_all();
             if (rc != KQ_OK) throw std::runtime_error("Error: " + err);
             return;
@@ -393,7 +396,7 @@ struct GpuSink {
             const auto t0 = std::chrono::steady_clock::now();
             std::unique_lock<std::mutex> l(m);
             for (;;) {
-                if (failed) throw std::runtime_error("read ingest aborted");      // (the first failure is the one reported)
+                if (failed) throw std::runtime_error(cause.empty() ? "read ingest aborted" : cause);      // (the first failure is the one reported)
                 if (!free_list.empty()) break;
                 if (!flying.empty()) {                                // the oldest copy in flight: wait for it outside the lock
                     const int i = flying.front();
@@ -404,7 +407,7 @@ struct GpuSink {
                     const std::string werr = wrc != KQ_OK ? kq_last_error() : "";
                     l.lock();
                     free_list.push_back(i);                           // back to the pool whatever happened
-                    if (wrc != KQ_OK) { failed = true; cv.notify_all(); throw std::runtime_error("Error: " + werr); }
+                    if (wrc != KQ_OK) { set_failed("Error: " + werr); cv.notify_all(); throw std::runtime_error("Error: " + werr); }
                     cv.notify_one();
                     continue;
                 }
@@ -414,7 +417,7 @@ struct GpuSink {
             free_list.pop_back();
             l.unlock();
             try { materialize(pool[i]); }
-            catch (...) { { std::lock_guard<std::mutex> g(m); free_list.push_back(i); failed = true; } cv.notify_all(); throw; }
+            catch (const std::exception& e) { { std::lock_guard<std::mutex> g(m); free_list.push_back(i); set_failed(e.what()); } cv.notify_all(); throw; }
             ns_wait += (std::chrono::steady_clock::now() - t0).count();
             *c = cap;
             return pool[i].ascii;
@@ -426,7 +429,7 @@ struct GpuSink {
         // are seen exactly once, kreeq_amd.hip count_seq_dev)
         bs.acquire_big = [this](unsigned, size_t n) {
             char* p = (char*)kq_host_alloc(n);
-            if (!p) { fail(); throw std::runtime_error("read buffer allocation failed (" + std::to_string(n) + " bytes)"); }
+            if (!p) { const std::string why = "read buffer allocation failed (" + std::to_string(n) + " bytes)"; fail(why); throw std::runtime_error(why); }
             return p;
         };
         bs.submit_big = [this](unsigned, char* buf, size_t len) {
@@ -435,7 +438,7 @@ struct GpuSink {
             std::string err = rc != KQ_OK ? kq_last_error() : "";
             if (rc == KQ_OK && len) { rc = kq_host_wait(h, tk); if (rc != KQ_OK) err = kq_last_error(); }
             kq_host_free(buf);
-            if (rc != KQ_OK) { fail(); throw std::runtime_error("Error: " + err); }
+            if (rc != KQ_OK) { fail("Error: " + err); throw std::runtime_error("Error: " + err); }
             ++n_submit;
         };
         bs.abort = [this] { fail(); };

@@ -221,6 +221,41 @@ def de_bruijn_linear(k):
     return ACGT[np.concatenate([s, s[:k - 1]])].tobytes()
 
 
+def branch_flags(entries, k, seq, cov_cutoff=0):
+    """kq_branch_scan's answer from a table export: per position of seq, bit 0 = the k-mer that starts there is in the
+    table, bit 1 = searchVariants has a candidate at depth 0 there: an edge that passes the test of oracle/variants.py:255
+    -- `fw[i] != 0` on the forward strand, `bw[i] > cov_cutoff` on the reverse strand (the reference's precedence,
+    src/variants.cpp:237) -- towards another base than the one seq has next.  Positions without a k-mer are 0."""
+    from oracle import variants as V
+
+    row = {key: i for i, key in enumerate(entries["key"].tolist())}
+    fw_counts, bw_counts = entries["fw"].tolist(), entries["bw"].tolist()
+    codes = [V.CTOI.get(chr(c), 4) for c in seq]
+    want = np.zeros(len(seq), dtype=np.uint8)
+    mask, run, fwd, rev = (1 << (2 * k)) - 1, 0, 0, 0
+    for end, code in enumerate(codes):                       # V.hash_kmer of codes[c:c + k], rolled from base to base
+        if code == 4:
+            run = fwd = rev = 0
+            continue
+        run += 1
+        fwd = (fwd >> 2) | (code << (2 * k - 2))
+        rev = ((rev << 2) | (3 - code)) & mask
+        if run < k:
+            continue
+        c = end - k + 1
+        key, fw = (fwd, True) if fwd < rev else (rev, False)
+        if key in row:
+            f = 1
+            nxt = codes[c + k] if c + k < len(seq) else 4
+            fwc, bwc = fw_counts[row[key]], bw_counts[row[key]]
+            for i in range(4):
+                edge = (fwc[i] != 0) if fw else (bwc[i] > cov_cutoff)
+                if edge and (i if fw else 3 - i) != nxt:
+                    f |= 2
+            want[c] = f
+    return want
+
+
 def revcomp_bases(seq: bytes):
     return seq[::-1].translate(bytes.maketrans(b"ACGTacgt", b"TGCAtgca"))
 

@@ -759,8 +759,6 @@ def test_partitioned_paths_degenerate_inputs(kq, O):
 def test_lookup_keys_and_branch_scan(kq, O):
     """kq_lookup_keys == map->find per key (present and absent keys, a high-copy k-mer included); kq_branch_scan flags
     = (present, searchVariants has a candidate at depth 0) per position, checked against the oracle's table"""
-    from oracle import variants as V
-
     k = 21
     batch, genome = H.synth_reads(3000, 150, 40000, seed=61, err=0.01)
     hot = b"\n".join([b"ACGTTGCA" * 19] * 300)
@@ -785,22 +783,9 @@ def test_lookup_keys_and_branch_scan(kq, O):
     seq[5000] = ord("N")
     seq = bytes(seq)
     flags = gpu.branch_scan(seq)
-    g = V.Graph(want, k)
-    codes = [V.CTOI.get(chr(c), 4) for c in seq]
+    expect = H.branch_flags(want, k, seq)
     for c in range(len(seq)):
-        window = codes[c:c + k]
-        f = 0
-        if len(window) == k and 4 not in window:
-            key, fw = V.hash_kmer(window, k)
-            if key in g.nodes:
-                f = 1
-                nxt = codes[c + k] if c + k < len(seq) else 4
-                fwc, bwc, _ = g.nodes[key]
-                for i in range(4):
-                    edge = fwc[i] != 0 if fw else bwc[i] > 0
-                    if edge and (i if fw else 3 - i) != nxt:
-                        f |= 2
-        assert flags[c] == f, (c, flags[c], f)
+        assert flags[c] == expect[c], (c, flags[c], expect[c])
 
 
 @pytest.mark.parametrize("k,hint,n_parts,n_peers", [(21, 5_000_000, 3, 2), (21, 40_000_000, 8, 3), (17, 5_000_000, 2, 1), (21, 5_870_000, 5, 4),

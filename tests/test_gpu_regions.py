@@ -295,8 +295,6 @@ def test_full_regions_count(kq, O, k, cls):
 
 @pytest.mark.parametrize("k,cls", FULL_CASES, ids=[f"k{k}-{c}" for k, c in FULL_CASES])
 def test_full_regions_lookup(kq, O, k, cls):
-    from oracle import variants as V
-
     ref = full_or_skip(k, cls)
     db = handle(kq, k, cls, count_path="partitioned")
     for b in ref.batches:
@@ -321,24 +319,7 @@ def test_full_regions_lookup(kq, O, k, cls):
     # branch_scan: (present, a continuation other than the next base) per position, from the oracle's table
     seq = ref.asm[:6000 * (k + 3) // 8]
     flags = db.branch_scan(seq)
-    g = V.Graph(ref.export, k)
-    codes = [V.CTOI.get(chr(c), 4) for c in seq]
-    want = np.zeros(len(seq), dtype=np.uint8)
-    for c in range(len(seq) - k + 1):
-        window = codes[c:c + k]
-        if 4 in window:
-            continue
-        key, fw = V.hash_kmer(window, k)
-        if key in g.nodes:
-            f = 1
-            nxt = codes[c + k] if c + k < len(seq) else 4
-            fwc, bwc, _ = g.nodes[key]
-            for i in range(4):
-                edge = fwc[i] != 0 if fw else bwc[i] > 0
-                if edge and (i if fw else 3 - i) != nxt:
-                    f |= 2
-            want[c] = f
-    assert np.array_equal(flags, want)
+    assert np.array_equal(flags, H.branch_flags(ref.export, k, seq))
     db.close()
 
 
