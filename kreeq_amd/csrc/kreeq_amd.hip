@@ -111,6 +111,12 @@ static int scr_ensure(Scrambled& b, size_t need, int device) {
     return KQ_OK;
 }
 
+// a device buffer grown on demand (ensure_buf); freed by kq_destroy, which sets the device first
+struct DevBuf { void* p = nullptr; size_t bytes = 0; };
+// the scratch of one partition plan (plan_alloc): record buffers + offsets, and the second record array of large plans (the
+// middle level's output)
+struct ScratchSet { DevBuf part; Scrambled part2; };
+
 struct kq_handle;
 static void arena_release(kq_handle* h);
 struct kq_handle {
@@ -129,8 +135,8 @@ struct kq_handle {
     DevState* st = nullptr;          // device
     DevState* st_host = nullptr;     // pinned mirror
     // scratch (grown on demand)
-    void* scratch = nullptr; size_t scratch_bytes = 0;
-    void* stage = nullptr; size_t stage_bytes = 0;     // device staging for host-buffer entry points
+    DevBuf scratch;
+    DevBuf stage;                    // device staging for host-buffer entry points
     uint64_t kmers_bound = 0;        // upper bound of instances inserted (sizing the side table)
     uint64_t used_bound = 0;         // upper bound of occupied slots (skips the state read-back)
     uint64_t hc_check_at = 0;        // instance count from which the side table's fill is looked at again (reserve)
@@ -146,15 +152,13 @@ struct kq_handle {
     uint32_t filt_lo = 0, filt_hi = 0;   // KQ_OPT_COUNT_MAP_RANGE (set to [0, map_count) at creation)
     bool profile = false;                // KQ_OPT_PROFILE: HIP events around the stages of the partitioned count
     std::vector<std::pair<const char*, hipEvent_t>> marks;
-    void* part = nullptr; size_t part_bytes = 0;       // partitioned path: record buffers + offsets
-    Scrambled part2, fork_part2;                       // the second record array of large plans (the middle level's output), and the fork's
+    ScratchSet work, fork_work;                        // partitioned path: the scratch plans are carved from, and the fork's
     // Fork / join of the slices of ONE count call (see count_seq_dev): consecutive slices run their partition stages on two
     // internal streams with a scratch set each, so that slice j+1's P1 fills the issue slots slice j's levels leave idle.
     // `stream` is where launches go (a fork stream while a forked slice is being enqueued), `base` the handle's stream
     // (its own or the caller's): everything that reads the table or the device state runs there, behind a join.
     hipStream_t base = nullptr;
     hipStream_t fork_stream[2] = {nullptr, nullptr};
-    void* fork_part[2] = {nullptr, nullptr}; size_t fork_part_bytes[2] = {0, 0};      // [0] aliases part / part_bytes while a forked slice runs
     bool fork_busy[2] = {false, false};              // work enqueued on the fork stream that `base` has not been joined with
     bool fork_stale[2] = {false, false};             // a table pass was enqueued on `base` since the fork stream last waited for one
     static constexpr int EV_RING = 64;
@@ -182,7 +186,7 @@ struct kq_handle {
     // pipelined host ingest (kq_count_batch_async): copies on their own stream into a ring of device staging buffers
     static constexpr int IN_SLOTS = 3, IN_TICKETS = 512;
     hipStream_t copy_stream = nullptr;
-    void* in_buf[IN_SLOTS] = {nullptr, nullptr, nullptr}; size_t in_bytes[IN_SLOTS] = {0, 0, 0};
+    DevBuf in_buf[IN_SLOTS];
     hipEvent_t in_consumed[IN_SLOTS] = {nullptr, nullptr, nullptr};      // the count that read the slot has been enqueued and finished
     std::vector<hipEvent_t> in_copied;   // ring of "copy of ticket t done" events
     uint64_t in_next = 0;
@@ -190,16 +194,14 @@ struct kq_handle {
     uint8_t in_bad[IN_TICKETS] = {};     // format (KQ_FASTX_*) whose rules the text of a ticket broke (kq_count_fastx_async), else 0
     // device FASTQ / FASTA parser (kq_fastx.h): unit summaries, the compact read batch of kq_count_fastx_dev and, per ring
     // slot, of kq_count_fastx_async (the slot's in_buf keeps the raw text), the chain's result and its page-locked mirror
-    void* fx_units = nullptr; size_t fx_units_bytes = 0;
-    void* fx_out = nullptr; size_t fx_out_bytes = 0;
-    void* in_cmp[IN_SLOTS] = {nullptr, nullptr, nullptr}; size_t in_cmp_bytes[IN_SLOTS] = {0, 0, 0};
+    DevBuf fx_units, fx_out, in_cmp[IN_SLOTS];
     FxResult* fx_res = nullptr;          // device
     FxResult* fx_res_host = nullptr;     // pinned
     int fx_bad = 0;                      // a counted text broke its format: reported by kq_sync until kq_clear
     bool hist_cache_off = false;         // the batch being counted lives in a library-owned buffer, which keeps its address and
                                          // changes its content: the address-keyed KQ_OPT_COUNT_MAP_PASSES cache must not see it
     bool test_fail_plan = false;         // KQ_OPT_TEST_FAIL_PLAN: the next partition plan fails with KQ_ERR_NOMEM (failure-path tests)
-    void* hot = nullptr; size_t hot_bytes = 0;         // k_count_regions' list of skewed regions
+    DevBuf hot;                          // k_count_regions' list of skewed regions
 
     TableView view() const {
         TableView v; v.slots = slots - (reg_lo() << REGION_SHIFT); v.n_regions = n_regions; v.hc = hc; v.hc_mask = hc_cap - 1; v.st = st; v.k = (uint32_t)k;
@@ -255,12 +257,12 @@ static void arena_release(kq_handle* h) {
     if (h->arena_scr.p) scr_free(h->arena_scr); else (void)hipFree(h->arena);
     h->arena = nullptr; h->arena_bytes = 0;
 }
-static int ensure_buf(void** p, size_t* have, size_t need) {
-    if (*have >= need) return KQ_OK;
-    if (*p) { HIPC(hipFree(*p)); *p = nullptr; *have = 0; }
+static int ensure_buf(DevBuf& b, size_t need) {
+    if (b.bytes >= need) return KQ_OK;
+    if (b.p) { HIPC(hipFree(b.p)); b = DevBuf(); }
     size_t sz = need + std::min<size_t>(need / 4, (size_t)256 << 20) + 4096;      // geometric growth for small buffers, bounded slack for multi-GB ones
-    HIPC(hipMalloc(p, sz));
-    *have = sz;
+    HIPC(hipMalloc(&b.p, sz));
+    b.bytes = sz;
     return KQ_OK;
 }
 
@@ -402,10 +404,10 @@ static inline void aligned_view(const char* d, const uint8_t** ab, uint64_t* lea
 }
 
 static int stage_in(kq_handle* h, const void* host, size_t bytes, void** dev) {
-    int rc = ensure_buf(&h->stage, &h->stage_bytes, bytes + 64);
+    int rc = ensure_buf(h->stage, bytes + 64);
     if (rc) return rc;
-    if (bytes) HIPC(hipMemcpyAsync(h->stage, host, bytes, hipMemcpyHostToDevice, h->stream));
-    *dev = h->stage;
+    if (bytes) HIPC(hipMemcpyAsync(h->stage.p, host, bytes, hipMemcpyHostToDevice, h->stream));
+    *dev = h->stage.p;
     return KQ_OK;
 }
 
@@ -556,26 +558,26 @@ void kq_destroy(kq_handle* h) {
     if (h->hc) (void)hipFree(h->hc);
     if (h->st) (void)hipFree(h->st);
     if (h->st_host) (void)hipHostFree(h->st_host);
-    if (h->scratch) (void)hipFree(h->scratch);
-    if (h->stage) (void)hipFree(h->stage);
-    if (h->part) (void)hipFree(h->part);
-    scr_free(h->part2); scr_free(h->fork_part2);
+    if (h->scratch.p) (void)hipFree(h->scratch.p);
+    if (h->stage.p) (void)hipFree(h->stage.p);
+    if (h->work.part.p) (void)hipFree(h->work.part.p);
+    scr_free(h->work.part2); scr_free(h->fork_work.part2);
     for (auto& e : h->hist_cache) (void)hipFree(e.m1_all);
     for (int w = 0; w < 2; ++w) { if (h->fork_stream[w]) { (void)hipStreamSynchronize(h->fork_stream[w]); (void)hipStreamDestroy(h->fork_stream[w]); } }
-    if (h->fork_part[1]) (void)hipFree(h->fork_part[1]);
+    if (h->fork_work.part.p) (void)hipFree(h->fork_work.part.p);
     for (auto e : h->ev_ring) if (e) (void)hipEventDestroy(e);
     if (h->ev_pass) (void)hipEventDestroy(h->ev_pass);
-    for (int i = 0; i < kq_handle::IN_SLOTS; ++i) { if (h->in_buf[i]) (void)hipFree(h->in_buf[i]); if (h->in_consumed[i]) (void)hipEventDestroy(h->in_consumed[i]); }
+    for (int i = 0; i < kq_handle::IN_SLOTS; ++i) { if (h->in_buf[i].p) (void)hipFree(h->in_buf[i].p); if (h->in_consumed[i]) (void)hipEventDestroy(h->in_consumed[i]); }
     for (auto e : h->in_copied) (void)hipEventDestroy(e);
-    for (int i = 0; i < kq_handle::IN_SLOTS; ++i) if (h->in_cmp[i]) (void)hipFree(h->in_cmp[i]);
-    if (h->fx_units) (void)hipFree(h->fx_units);
-    if (h->fx_out) (void)hipFree(h->fx_out);
+    for (int i = 0; i < kq_handle::IN_SLOTS; ++i) if (h->in_cmp[i].p) (void)hipFree(h->in_cmp[i].p);
+    if (h->fx_units.p) (void)hipFree(h->fx_units.p);
+    if (h->fx_out.p) (void)hipFree(h->fx_out.p);
     if (h->fx_res) (void)hipFree(h->fx_res);
     if (h->fx_res_host) (void)hipHostFree(h->fx_res_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     arena_release(h);
     if (h->d_sets) (void)hipFree(h->d_sets);
-    if (h->hot) (void)hipFree(h->hot);
+    if (h->hot.p) (void)hipFree(h->hot.p);
     marks_reset(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
@@ -709,11 +711,14 @@ struct PartPlan {
     uint64_t n_max, R;
     uint32_t g1;              // P1 scatter workgroups
     uint64_t m1_n, m2_n, sums_n, groups_n;
-    // device pointers into h->part
+    // device pointers into h->work
     uint64_t *recs1, *recs2;
     uint8_t *aux1, *aux2;     // WIDE records: edge bytes travelling with recs1 / recs2
     unsigned long long *m1, *seg_off, *unit_base, *group_base, *sums, *total, *hot;
     uint32_t* m2;
+    // the lockstep bytes of recs1 / recs2; null for the formats that have none
+    uint8_t* a1() const { return fmt == FMT_WIDE || fmt == FMT_NARROW ? aux1 : nullptr; }
+    uint8_t* a2() const { return fmt == FMT_WIDE || fmt == FMT_NARROW ? aux2 : nullptr; }
 };
 static void plan_cfg(const kq_handle* h, PartCfg* cfg, bool allow_narrow = false) {
     cfg->n_regions = h->n_regions;
@@ -770,14 +775,14 @@ static int plan_alloc(kq_handle* h, PartPlan* p, uint64_t n_max, uint64_t n_tile
     const uint64_t rec_words = p->fmt == FMT_NARROW ? n_max / 2 + 2 : n_max;          // narrow records: u32 + lockstep byte
     // the second record array of a large plan lives in a physically scrambled buffer of its own (struct Scrambled)
     const bool split2 = (rec_words + aux_words) * 8 >= ((size_t)512 << 20);
-    if (split2) { int rc2 = scr_ensure(h->part2, (size_t)(rec_words + aux_words) * 8, h->device); if (rc2) return rc2; }
+    if (split2) { int rc2 = scr_ensure(h->work.part2, (size_t)(rec_words + aux_words) * 8, h->device); if (rc2) return rc2; }
     const size_t words = (size_t)((split2 ? 1 : 2) * (rec_words + aux_words) + p->m1_n + 2 * (seg_max + 2) + p->groups_n + p->sums_n + 4 + (p->R + 2) + (p->m2_n + 1) / 2);
-    int rc = ensure_buf(&h->part, &h->part_bytes, words * 8);
+    int rc = ensure_buf(h->work.part, words * 8);
     if (rc) return rc;
-    p->recs1 = (uint64_t*)h->part;
+    p->recs1 = (uint64_t*)h->work.part.p;
     p->aux1 = (uint8_t*)(p->recs1 + rec_words);
     uint64_t* rest = (uint64_t*)(p->aux1 + aux_words * 8);
-    if (split2) { p->recs2 = (uint64_t*)h->part2.p; p->aux2 = (uint8_t*)(p->recs2 + rec_words); }
+    if (split2) { p->recs2 = (uint64_t*)h->work.part2.p; p->aux2 = (uint8_t*)(p->recs2 + rec_words); }
     else { p->recs2 = rest; p->aux2 = (uint8_t*)(p->recs2 + rec_words); rest = (uint64_t*)(p->aux2 + aux_words * 8); }
     p->m1 = (unsigned long long*)rest;
     p->seg_off = p->m1 + p->m1_n;
@@ -904,27 +909,31 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
 #undef KQ_P1T
     mark(h, "k_p1_scatter");
 }
-// one generic split level: in (grouped by p->seg_off[0..n_seg]) -> out grouped by (segment, bin);
-// afterwards p->group_base[0..n_seg*nb] are the output offsets
-static void run_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const uint64_t* in, const uint8_t* in_aux, uint64_t* out, uint8_t* out_aux,
-                      unsigned long long* gb = nullptr /*where the output offsets go (default p->group_base)*/,
-                      const unsigned long long* seg_hi = nullptr /*end of every input segment (default: the next one's start)*/) {
+// The input of a split level: records (+ lockstep bytes) grouped in segments [seg_lo[i], seg_hi[i]).  n_seg / spb (segments per
+// hash-prefix bucket) matter to sort_to_regions only, whose first level may read runs that are not the plan's own
+struct LevelIn { const uint64_t* recs; const uint8_t* aux; const unsigned long long *seg_lo, *seg_hi; uint32_t n_seg, spb; };
+// records grouped by the plan's own segment table p.seg_off[0..n_seg]: every segment ends where the next one starts
+static LevelIn own_segments(const PartPlan& p, const uint64_t* recs, const uint8_t* aux, uint32_t n_seg) { return LevelIn{recs, aux, p.seg_off, p.seg_off + 1, n_seg, 1}; }
+// one generic split level: src -> out grouped by (segment, bin); afterwards gb[0..n_seg*nb] are the output offsets
+static void run_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const LevelIn& src, uint64_t* out, uint8_t* out_aux,
+                      unsigned long long* gb = nullptr /*where the output offsets go (default p->group_base)*/) {
     if (!gb) gb = p->group_base;
-    if (!seg_hi) seg_hi = p->seg_off + 1;
+    const uint64_t* in = src.recs; const uint8_t* in_aux = src.aux;
+    const unsigned long long *seg_lo = src.seg_lo, *seg_hi = src.seg_hi;
     LevelCfg lvr = lv;                                            // rank replication: as many counters per bin as fit 512 (at most 64, one per lane)
     lvr.rep_shift = 0;
     while (lvr.rep_shift < 6 && (((uint64_t)lv.nb + 1) << (lvr.rep_shift + 1)) <= 512) ++lvr.rep_shift;
     const LevelCfg& lv_ = lvr;
     const int fmt = lv.narrow == 2 ? FMT_TOP8 : lv.narrow ? FMT_NARROW : in_aux != nullptr ? FMT_WIDE : FMT_PACK8;       // input format; lv.top8: packed in, narrow out
     const uint64_t groups = (uint64_t)(lv.n_seg / lv.spb) * lv.nb;
-    hipLaunchKernelGGL(k_lv_units, dim3(1), dim3(1024), 0, h->stream, p->seg_off, seg_hi, lv_, p->unit_base);
+    hipLaunchKernelGGL(k_lv_units, dim3(1), dim3(1024), 0, h->stream, seg_lo, seg_hi, lv_, p->unit_base);
     // one workgroup per work unit (upper bound of the unit count; surplus workgroups exit at once):
     // the hardware dispatcher balances them, a fixed grid looping over units left a 30 % tail
     const unsigned unit_grid = (unsigned)std::min<uint64_t>(p->n_max / P2_UNIT + lv.n_seg + 1, 1u << 30);
-    if (fmt == FMT_TOP8) hipLaunchKernelGGL(k_lv_hist<FMT_TOP8>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, p->seg_off, seg_hi, p->unit_base, p->m2);
-    else if (fmt == FMT_NARROW) hipLaunchKernelGGL(k_lv_hist<FMT_NARROW>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, p->seg_off, seg_hi, p->unit_base, p->m2);
-    else if (fmt == FMT_WIDE) hipLaunchKernelGGL(k_lv_hist<FMT_WIDE>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, p->seg_off, seg_hi, p->unit_base, p->m2);
-    else hipLaunchKernelGGL(k_lv_hist<FMT_PACK8>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, p->seg_off, seg_hi, p->unit_base, p->m2);
+    if (fmt == FMT_TOP8) hipLaunchKernelGGL(k_lv_hist<FMT_TOP8>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, seg_lo, seg_hi, p->unit_base, p->m2);
+    else if (fmt == FMT_NARROW) hipLaunchKernelGGL(k_lv_hist<FMT_NARROW>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, seg_lo, seg_hi, p->unit_base, p->m2);
+    else if (fmt == FMT_WIDE) hipLaunchKernelGGL(k_lv_hist<FMT_WIDE>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, seg_lo, seg_hi, p->unit_base, p->m2);
+    else hipLaunchKernelGGL(k_lv_hist<FMT_PACK8>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, seg_lo, seg_hi, p->unit_base, p->m2);
     // few units per segment (many segments): one thread per group; else one wave per group (a segment of thousands of units)
     if (p->n_max / P2_UNIT + 1 <= 8 * (uint64_t)(lv.n_seg / lv.spb))
         hipLaunchKernelGGL(k_lv_offsets_thread, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, h->stream, p->m2, lv_, p->unit_base, gb);
@@ -935,12 +944,12 @@ static void run_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const uint6
     mark(h, "k_lv_hist+offsets+scan");
     const bool small = lv.nb < 512;
 #define KQ_LVS(W, N) hipLaunchKernelGGL((k_lv_scatter<W, N>), dim3(unit_grid), dim3(LV_THREADS), 0, h->stream, in, in_aux, lv_, \
-                                        p->seg_off, seg_hi, p->unit_base, p->m2, gb, out, out_aux)
+                                        seg_lo, seg_hi, p->unit_base, p->m2, gb, out, out_aux)
     if (lv.top8)              { KQ_LVS(FMT_PACK8_TO_NARROW, 512); }
     else if (fmt == FMT_TOP8) { if (small) KQ_LVS(FMT_TOP8, 512); else KQ_LVS(FMT_TOP8, NB_MAX); }
     // narrow records, at most 512 (bin, replica) counters: the streamed scatter (k_lv_scatter_s) for the level that writes tight records
 #define KQ_LVN(T) hipLaunchKernelGGL((k_lv_scatter_s<T>), dim3(unit_grid), dim3(LV_THREADS), 0, h->stream, (const uint32_t*)in, in_aux, lv_, \
-                                      p->seg_off, seg_hi, p->unit_base, p->m2, gb, (uint32_t*)out, out_aux)
+                                      seg_lo, seg_hi, p->unit_base, p->m2, gb, (uint32_t*)out, out_aux)
     else if (fmt == FMT_NARROW && small && lv.rstart && !(h->kernel_set & 4)) { KQ_LVN(true); }
     else if (fmt == FMT_NARROW && small && !lv.rstart && (h->kernel_set & 2)) { KQ_LVN(false); }     // (measured: 0 .. +8 % against k_lv_scatter; not the default)
 #undef KQ_LVN
@@ -974,9 +983,6 @@ static LevelCfg level_narrow(const PartCfg& cfg, uint32_t sub_bits = 0, bool mid
     lv.spb = 1;
     return lv;
 }
-// bucket -> regions for FMT_NARROW records, in one level or (large tables) two; afterwards `*sorted` holds the
-// records grouped by region and p->group_base their offsets
-static void run_narrow_levels(kq_handle* h, PartPlan* p, const uint64_t** sorted, const uint8_t** sorted_aux, const P3Set* dst = nullptr, bool tight = false);
 // FMT_TIGHT output of the last split level (count path only: the lookup kernels read 5-byte records)
 static bool tight_ok(const kq_handle* h, const PartPlan& p) { return p.fmt == FMT_NARROW && p.R >= TIGHT_MIN_REGIONS && h->rstart != nullptr; }
 static LevelCfg level_flat_to_coarse(const PartCfg& cfg) {
@@ -996,16 +1002,32 @@ static LevelCfg level_flat_to_coarse(const PartCfg& cfg) {
 // per slice; KQ_OPT_PENDING_BYTES bounds the arena (0 = apply every slice at once, the round-1 behaviour).
 __global__ void k_p3set(P3Set* sets, int i, P3Set v) { sets[i] = v; }
 
-static size_t set_bytes(uint64_t n_max, int fmt, uint64_t R) {
+// layout of one pending set of at most n_max records: the records, their lockstep bytes (formats that have them), R + 2 region offsets
+struct SetLayout { bool has_aux; size_t aux_off /*= the record bytes*/, base_off, total; };
+static SetLayout set_bytes(uint64_t n_max, int fmt, uint64_t R) {
     const size_t rec = (fmt == FMT_NARROW || fmt == FMT_TIGHT) ? 4 : 8;
-    const bool aux = fmt == FMT_NARROW || fmt == FMT_WIDE;
-    return ((((size_t)n_max * rec + 63) & ~(size_t)63) + (aux ? (((size_t)n_max + 63) & ~(size_t)63) : 0) + (size_t)(R + 2) * 8 + 255) & ~(size_t)255;
+    SetLayout l;
+    l.has_aux = fmt == FMT_NARROW || fmt == FMT_WIDE;
+    l.aux_off = ((size_t)n_max * rec + 63) & ~(size_t)63;
+    l.base_off = l.aux_off + (l.has_aux ? ((size_t)n_max + 63) & ~(size_t)63 : 0);
+    l.total = (l.base_off + (size_t)(R + 2) * 8 + 255) & ~(size_t)255;
+    return l;
 }
-// room for one more set in the arena (flushes / allocates as needed); false: no deferral for this slice
-static int arena_take(kq_handle* h, uint64_t n_max, int fmt, uint64_t R, P3Set* out, bool* ok) {
-    *ok = false;
+// Where the last split level writes records, lockstep bytes and region offsets: a pending set in the arena (recs != nullptr) or
+// the plan's scratch, whose set is applied at once (the scratch is reused by the next slice).  fmt / aux_fmt: of the finished
+// set; `tight`: the last level writes FMT_TIGHT records (count path only: the lookup kernels read 5-byte records)
+struct Dest {
+    int fmt, aux_fmt;
+    bool tight = false;
+    uint64_t* recs = nullptr; uint8_t* aux = nullptr; unsigned long long* base = nullptr; uint64_t n_max = 0;      // the arena set
+    bool in_arena() const { return recs != nullptr; }
+};
+// room for one more set of format d->fmt in the arena (flushes / allocates as needed); d stays in the scratch: no deferral for this slice
+static int arena_take(kq_handle* h, uint64_t n_max, uint64_t R, Dest* d) {
     if (h->pend_budget == 0) return KQ_OK;
-    const size_t need = set_bytes(n_max, fmt, R);
+    const int fmt = d->fmt;
+    const SetLayout lay = set_bytes(n_max, fmt, R);
+    const size_t need = lay.total;
     bool was_full = false;
     if (h->n_pend && (h->n_pend >= P3_MAX_SETS || h->pend_fmt != fmt || h->arena_used + need > h->arena_bytes)) {
         was_full = h->pend_fmt == fmt && h->n_pend < P3_MAX_SETS;
@@ -1038,17 +1060,12 @@ static int arena_take(kq_handle* h, uint64_t n_max, int fmt, uint64_t R, P3Set* 
             h->arena_bytes = budget; h->arena_used = 0;
         }
     }
-    uint8_t* base = (uint8_t*)h->arena + h->arena_used;
-    const size_t rec = (fmt == FMT_NARROW || fmt == FMT_TIGHT) ? 4 : 8;
-    const bool aux = fmt == FMT_NARROW || fmt == FMT_WIDE;
-    out->recs = (const uint64_t*)base;
-    base += ((size_t)n_max * rec + 63) & ~(size_t)63;
-    out->aux = aux ? base : nullptr;
-    if (aux) base += ((size_t)n_max + 63) & ~(size_t)63;
-    out->base = (const unsigned long long*)base;
-    out->n_max = n_max;
+    uint8_t* set = (uint8_t*)h->arena + h->arena_used;
+    d->recs = (uint64_t*)set;
+    d->aux = lay.has_aux ? set + lay.aux_off : nullptr;
+    d->base = (unsigned long long*)(set + lay.base_off);
+    d->n_max = n_max;
     h->arena_used += need;
-    *ok = true;
     return KQ_OK;
 }
 // make `set` (records of format fmt, sorted by region of the CURRENT geometry) part of the next table pass
@@ -1083,14 +1100,14 @@ static int flush_pending(kq_handle* h) {
 }
 static int flush_pending_base(kq_handle* h) {
     const uint64_t R = h->n_regions;
-    int rc = ensure_buf(&h->hot, &h->hot_bytes, (size_t)(R + 2) * 8);
+    int rc = ensure_buf(h->hot, (size_t)(R + 2) * 8);
     if (rc) return rc;
     if (h->kmers_bound / 255 + 1 > (1ull << 23)) {       // large jobs: the side table follows its observed fill (see reserve)
         rc = read_state_raw(h); if (rc) return rc;
         const uint64_t need_hc = std::max<uint64_t>(HC_CAP_BIG, 8 * h->st_host->hc_used);
         if (need_hc > h->hc_cap) { rc = grow_hc(h, need_hc); if (rc) return rc; }
     }
-    unsigned long long* hot = (unsigned long long*)h->hot;       // [0] = count, then up to R region ids
+    unsigned long long* hot = (unsigned long long*)h->hot.p;     // [0] = count, then up to R region ids
     HIPC(hipMemsetAsync(hot, 0, 8, h->stream));
     const dim3 grid((unsigned)std::min<uint64_t>(h->n_alloc_regions(), 1u << 30)), grid_hot(h->n_cu), block(P3_THREADS);   // one workgroup per (allocated) region: dispatcher-balanced
     // 1: the slot array holds the empty image (skip reading it); 2: logically empty but not initialised (lazy kq_clear):
@@ -1134,78 +1151,94 @@ static bool part_table_ok(const kq_handle* h, bool narrow_possible) {
     PartCfg c; plan_cfg(h, &c, true);
     return c.narrow != 0;
 }
-// `dst` != nullptr: the last level writes records, lockstep bytes and region offsets there (a pending set in the arena)
-static void run_narrow_levels(kq_handle* h, PartPlan* p, const uint64_t** sorted, const uint8_t** sorted_aux, const P3Set* dst, bool tight) {
-    const uint32_t sb = p->cfg.sub_bits;
-    const bool t8 = p->fmt == FMT_TOP8;
-    uint8_t* a1 = t8 ? nullptr : p->aux1;
-    uint8_t* a2 = t8 ? nullptr : p->aux2;
-    uint64_t* fin = dst ? const_cast<uint64_t*>(dst->recs) : (sb == 0 ? p->recs2 : p->recs1);
-    uint8_t* fin_aux = (t8 || tight) ? nullptr : dst ? const_cast<uint8_t*>(dst->aux) : (sb == 0 ? a2 : a1);
-    unsigned long long* fin_base = dst ? const_cast<unsigned long long*>(dst->base) : p->group_base;
-    LevelCfg last = level_narrow(p->cfg, sb, false, t8);
-    if (tight) last.rstart = h->rstart;
-    if (sb == 0) {
-        run_level(h, p, last, p->recs1, a1, fin, fin_aux, fin_base);
+// the destination of the set the plan's levels make of at most n_max records: in the arena if it has (or gets) room, else the
+// scratch.  (A map-range pass calls this after P1, with the record count P1 found: see count_partitioned)
+static int dest_take(kq_handle* h, const PartPlan& p, uint64_t n_max, Dest* d) {
+    d->tight = tight_ok(h, p);
+    if (d->tight) { d->fmt = FMT_TIGHT; d->aux_fmt = AUX_TIGHT; }
+    return arena_take(h, n_max, p.R, d);
+}
+// Region-sorted set of records that the first split left grouped as `in`: whatever levels the plan needs, the last one
+// writing to `d`.
+//   5-byte / hash-remainder records (FMT_NARROW / FMT_TOP8): bucket -> regions (bucket b owns regions [b * nb, (b + 1) * nb)),
+//     in one level or, for plans with sub_bits, bucket -> sub-bucket -> regions
+//   packed / wide records: coarse bucket -> regions, or nothing at all when the bins were the regions themselves
+static P3Set sort_to_regions(kq_handle* h, PartPlan* p, const LevelIn& in, const Dest& d) {
+    const bool arena = d.in_arena();
+    uint64_t* fin = arena ? d.recs : p->recs2;
+    uint8_t* fin_aux = arena ? d.aux : p->a2();
+    unsigned long long* fin_base = arena ? d.base : p->group_base;
+    if (p->fmt == FMT_NARROW || p->fmt == FMT_TOP8) {
+        const uint32_t sb = p->cfg.sub_bits;
+        const bool t8 = p->fmt == FMT_TOP8;
+        // a middle level reads `in` and writes the scratch array that is not its input; the last level then takes the other one
+        const bool mid_to_2 = sb != 0 && in.recs == p->recs1;
+        if (!arena && mid_to_2) { fin = p->recs1; fin_aux = p->a1(); }
+        if (d.tight) fin_aux = nullptr;
+        LevelCfg last = level_narrow(p->cfg, sb, false, t8);
+        if (d.tight) last.rstart = h->rstart;
+        if (sb == 0) {
+            last.n_seg = in.n_seg; last.spb = in.spb;
+            run_level(h, p, last, in, fin, fin_aux, fin_base);
+        } else {
+            LevelCfg mid = level_narrow(p->cfg, sb, true, t8);
+            mid.n_seg = in.n_seg; mid.spb = in.spb;
+            uint64_t* m = mid_to_2 ? p->recs2 : p->recs1;
+            uint8_t* m_aux = mid_to_2 ? p->a2() : p->a1();
+            run_level(h, p, mid, in, m, m_aux);
+            (void)hipMemcpyAsync(p->seg_off, p->group_base, (size_t)(((1u << NARROW_CBITS) << sb) + 1) * 8, hipMemcpyDeviceToDevice, h->stream);
+            run_level(h, p, last, own_segments(*p, m, m_aux, last.n_seg), fin, fin_aux, fin_base);
+        }
+    } else if (p->two_level) {
+        run_level(h, p, level_coarse_to_regions(p->cfg), in, fin, fin_aux, fin_base);
     } else {
-        run_level(h, p, level_narrow(p->cfg, sb, true, t8), p->recs1, a1, p->recs2, a2);
-        (void)hipMemcpyAsync(p->seg_off, p->group_base, (size_t)(((1u << NARROW_CBITS) << sb) + 1) * 8, hipMemcpyDeviceToDevice, h->stream);
-        run_level(h, p, last, p->recs2, a2, fin, fin_aux, fin_base);
+        return P3Set{in.recs, in.aux, in.seg_lo, p->n_max};          // bins were the regions themselves
     }
-    *sorted = fin; *sorted_aux = fin_aux;
+    return P3Set{fin, fin_aux, fin_base, arena ? d.n_max : p->n_max};
 }
 
-// a set in the scratch buffers is applied at once (the scratch is reused by the next slice)
-static int pend_or_apply(kq_handle* h, const P3Set& set, int fmt, int aux_fmt, bool in_arena) {
-    int rc = pend_add(h, set, fmt, aux_fmt);
+// make `set` part of the next table pass; a set in the scratch buffers is applied at once (the scratch is reused by the next slice)
+static int submit(kq_handle* h, const P3Set& set, const Dest& d) {
+    HIPC(hipGetLastError());
+    int rc = pend_add(h, set, d.fmt, d.aux_fmt);
     if (rc) return rc;
-    return in_arena ? KQ_OK : flush_pending(h);
+    return d.in_arena() ? KQ_OK : flush_pending(h);
+}
+
+// the plan of a scanned sequence (count, region-wise lookup): 5-byte records up to k = 21 and 8-byte hash-remainder records
+// above k = 28 (tables with hash-prefix buckets), 8-byte packed records up to k = 28, hash + edge byte otherwise
+static int plan_sequence(kq_handle* h, PartPlan* p, uint64_t lead, uint64_t len) {
+    PartCfg c0; plan_cfg(h, &c0, true);
+    int rc = plan_alloc(h, p, len, n_tiles_of(lead, len), c0.n_coarse, true);
+    if (rc) return rc;
+    if (h->k > PART_MAX_K && p->fmt != FMT_TOP8) p->fmt = FMT_WIDE;
+    return KQ_OK;
 }
 
 // partitioned count of one batch of bases: P1 (coarse split) -> P2 (region split) -> a pending set for P3 (LDS regions)
 static int count_partitioned(kq_handle* h, const uint8_t* ab, uint64_t lead, uint64_t len, EmitRange er, const uint16_t* pinv = nullptr) {
     PartPlan p;
-    PartCfg c0; plan_cfg(h, &c0, true);
-    int rc = plan_alloc(h, &p, len, n_tiles_of(lead, len), c0.n_coarse, true);
+    int rc = plan_sequence(h, &p, lead, len);
     if (rc) return rc;
-    // 5-byte records up to k = 21 and 8-byte hash-remainder records above k = 28 (tables with hash-prefix buckets),
-    // 8-byte packed records up to k = 28, hash + edge byte otherwise
-    if (h->k > PART_MAX_K && p.fmt != FMT_TOP8) p.fmt = FMT_WIDE;
-    const bool has_aux = p.fmt == FMT_WIDE || p.fmt == FMT_NARROW;
-    uint8_t* a1 = has_aux ? p.aux1 : nullptr;
-    uint8_t* a2 = has_aux ? p.aux2 : nullptr;
     p.cfg.filt_lo = h->filt_lo; p.cfg.filt_hi = h->filt_hi;      // KQ_OPT_COUNT_MAP_RANGE
     if (h->windowed) { p.cfg.win_lo = h->win_lo; p.cfg.win_hi = h->win_hi; }      // a window drops foreign buckets in P1
     const bool leveled = p.fmt == FMT_NARROW || p.fmt == FMT_TOP8 || p.two_level;
-    P3Set set; bool in_arena = false;
-    const bool tight = tight_ok(h, p);
-    const int set_fmt = tight ? FMT_TIGHT : p.fmt;
+    Dest dst{p.fmt, AUX_IDX6};
     // A map-range pass (KQ_OPT_COUNT_MAP_RANGE: the reference's memory-bounded mode, src/kreeq.cpp:59-74) keeps a fraction of
     // the k-mers it scans: its pending set is sized by the record count P1 found, not by the starts of the slice, so that the
     // arena holds as many RECORDS per table pass as it would without the filter (one small read-back per slice)
     const bool filtered = p.cfg.filt_lo != 0 || p.cfg.filt_hi != p.cfg.map_count || h->windowed;      // (a window keeps its own buckets only)
-    if (leveled && !filtered) { rc = arena_take(h, p.n_max, set_fmt, p.R, &set, &in_arena); if (rc) return rc; }
+    if (leveled && !filtered) { rc = dest_take(h, p, p.n_max, &dst); if (rc) return rc; }
     marks_reset(h);
     mark(h, "start");
-    run_p1(h, &p, p.cfg, ab, lead, len, er, p.recs1, a1, AUX_IDX6, pinv);
+    run_p1(h, &p, p.cfg, ab, lead, len, er, p.recs1, p.a1(), AUX_IDX6, pinv);
     if (leveled && filtered) {
         unsigned long long n_recs = 0;
         HIPC(hipMemcpyAsync(&n_recs, p.total, sizeof n_recs, hipMemcpyDeviceToHost, h->stream));
         HIPC(hipStreamSynchronize(h->stream));
-        rc = arena_take(h, std::min<uint64_t>(p.n_max, ((uint64_t)n_recs + 15) & ~7ull), set_fmt, p.R, &set, &in_arena); if (rc) return rc;
+        rc = dest_take(h, p, std::min<uint64_t>(p.n_max, ((uint64_t)n_recs + 15) & ~7ull), &dst); if (rc) return rc;
     }
-    if (p.fmt == FMT_NARROW || p.fmt == FMT_TOP8) {
-        const uint64_t* sorted; const uint8_t* sorted_aux;
-        run_narrow_levels(h, &p, &sorted, &sorted_aux, in_arena ? &set : nullptr, tight);
-        if (!in_arena) set = P3Set{sorted, sorted_aux, p.group_base, p.n_max};
-    } else if (p.two_level) {
-        if (in_arena) run_level(h, &p, level_coarse_to_regions(p.cfg), p.recs1, a1, const_cast<uint64_t*>(set.recs), const_cast<uint8_t*>(set.aux), const_cast<unsigned long long*>(set.base));
-        else { run_level(h, &p, level_coarse_to_regions(p.cfg), p.recs1, a1, p.recs2, a2); set = P3Set{p.recs2, a2, p.group_base, p.n_max}; }
-    } else {
-        set = P3Set{p.recs1, a1, p.seg_off, p.n_max};          // bins were the regions themselves
-    }
-    HIPC(hipGetLastError());
-    return pend_or_apply(h, set, set_fmt, tight ? AUX_TIGHT : AUX_IDX6, in_arena);
+    return submit(h, sort_to_regions(h, &p, own_segments(p, p.recs1, p.a1(), p.cfg.n_coarse), dst), dst);
 }
 // partitioned count of n records already on the device (multi-GPU receive side, kq_insert_records_dev).
 // d_aux == nullptr: packed 8-byte records; else WIDE records with d_aux in `aux_fmt`.
@@ -1214,40 +1247,40 @@ static int count_partitioned_records(kq_handle* h, const uint64_t* d_recs, const
     PartPlan p;
     int rc = plan_alloc(h, &p, n, 0, 1, /*allow_narrow=*/!d_aux && !raw);
     if (rc) return rc;
-    P3Set set; bool in_arena = false;
+    if (d_aux) p.fmt = FMT_WIDE;
+    Dest dst{p.fmt, aux_fmt};
+    LevelCfg first = level_flat_to_coarse(p.cfg);
     if (p.fmt == FMT_NARROW) {
         // packed records of kq_emit_packed_dev on a narrow-eligible table: the first level splits on the top 8 hash
         // bits and writes 5-byte records, the rest is the narrow path of count_partitioned
-        const bool tight = tight_ok(h, p);
-        rc = arena_take(h, p.n_max, tight ? FMT_TIGHT : p.fmt, p.R, &set, &in_arena); if (rc) return rc;
-        hipLaunchKernelGGL(k_set2, dim3(1), dim3(1), 0, h->stream, p.seg_off, 0ull, (unsigned long long)n);
-        LevelCfg first = level_flat_to_coarse(p.cfg);
-        first.top8 = 1; first.nb = 1u << NARROW_CBITS;
-        run_level(h, &p, first, d_recs, nullptr, p.recs1, p.aux1);
-        HIPC(hipMemcpyAsync(p.seg_off, p.group_base, (size_t)((1u << NARROW_CBITS) + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
-        const uint64_t* sorted; const uint8_t* sorted_aux;
-        run_narrow_levels(h, &p, &sorted, &sorted_aux, in_arena ? &set : nullptr, tight);
-        if (!in_arena) set = P3Set{sorted, sorted_aux, p.group_base, p.n_max};
-        HIPC(hipGetLastError());
-        return pend_or_apply(h, set, tight ? FMT_TIGHT : FMT_NARROW, tight ? AUX_TIGHT : AUX_IDX6, in_arena);
+        rc = dest_take(h, p, p.n_max, &dst); if (rc) return rc;
+        first.top8 = 1;
+    } else {
+        first.in_raw = raw ? 1 : 0; first.k = (uint32_t)h->k;
     }
-    if (d_aux) p.fmt = FMT_WIDE;
-    uint8_t* a1 = d_aux ? p.aux1 : nullptr;
-    uint8_t* a2 = d_aux ? p.aux2 : nullptr;
     hipLaunchKernelGGL(k_set2, dim3(1), dim3(1), 0, h->stream, p.seg_off, 0ull, (unsigned long long)n);
-    LevelCfg first = level_flat_to_coarse(p.cfg);
-    first.in_raw = raw ? 1 : 0; first.k = (uint32_t)h->k;
-    run_level(h, &p, first, d_recs, d_aux, p.recs1, a1);        // group_base = coarse offsets
+    run_level(h, &p, first, own_segments(p, d_recs, d_aux, 1), p.recs1, p.a1());        // group_base = coarse offsets
+    LevelIn coarse{p.recs1, p.a1(), p.group_base, p.group_base + 1, p.cfg.n_coarse, 1};
     if (p.two_level) {
         // the coarse offsets become the segment table of the next level
         HIPC(hipMemcpyAsync(p.seg_off, p.group_base, (size_t)(p.cfg.n_coarse + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
-        run_level(h, &p, level_coarse_to_regions(p.cfg), p.recs1, a1, p.recs2, a2);
-        set = P3Set{p.recs2, a2, p.group_base, p.n_max};
-    } else {
-        set = P3Set{p.recs1, a1, p.group_base, p.n_max};
+        coarse = own_segments(p, p.recs1, p.a1(), p.cfg.n_coarse);
     }
-    HIPC(hipGetLastError());
-    return pend_or_apply(h, set, p.fmt, aux_fmt, false);
+    return submit(h, sort_to_regions(h, &p, coarse, dst), dst);
+}
+
+// the k-mer starts [a, b) of a resident sequence as a scan of their own (the margins: see count_seq_dev): ASCII bytes
+// (d_inv == nullptr) or the packed form, whose words hold 16 bases
+struct SliceView { const uint8_t* ab; const uint16_t* pinv; uint64_t lead, len; EmitRange er; };
+static SliceView slice_view(const char* d_bases, const uint16_t* d_inv, uint64_t len, int k, uint64_t a, uint64_t b) {
+    const uint64_t sub_off = a ? a - 1 : 0;
+    SliceView v;
+    v.len = std::min(len, b + k) - sub_off;
+    v.er = EmitRange{a - sub_off, b - sub_off};
+    v.pinv = nullptr;
+    if (d_inv) { v.ab = (const uint8_t*)(reinterpret_cast<const uint32_t*>(d_bases) + sub_off / 16); v.pinv = d_inv + sub_off / 16; v.lead = sub_off % 16; }
+    else aligned_view(d_bases + sub_off, &v.ab, &v.lead);
+    return v;
 }
 
 // count a resident sequence: ASCII bytes (d_inv == nullptr) or the packed form (d_bases = the code words, d_inv = the masks)
@@ -1275,13 +1308,13 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
             slice = (kmers + n_slices - 1) / n_slices;           // equal slices
             size_t free_b = 0, total_b = 0;
             if (cap == (1ull << 30) || slice <= (1ull << 30)) break;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + h->part_bytes >= (size_t)11 * slice + ((size_t)2 << 30)) break;   // the plan takes ~10.2 B per start
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + h->work.part.bytes >= (size_t)11 * slice + ((size_t)2 << 30)) break;   // the plan takes ~10.2 B per start
         }
     }
     if (h->pend_budget == 0 && !h->slice_user && kmers > slice && 2 * h->n_slots() > slice) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t by_mem = (uint64_t)((free_b + h->part_bytes) / 24);          // 16 B scratch + margin per start
+            const uint64_t by_mem = (uint64_t)((free_b + h->work.part.bytes) / 24);          // 16 B scratch + margin per start
             slice = std::max(slice, std::min<uint64_t>(std::min<uint64_t>(2 * h->n_slots(), 1ull << 31), by_mem));
         }
     }
@@ -1290,7 +1323,7 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
     // before the call returns -- the caller's stream-ordered view of the handle does not change, and no fork outlives a call.
     struct ForkGuard {
         kq_handle* h; bool swapped = false;
-        void leave() { if (swapped) { std::swap(h->part, h->fork_part[1]); std::swap(h->part_bytes, h->fork_part_bytes[1]); std::swap(h->part2, h->fork_part2); swapped = false; } h->stream = h->base; }
+        void leave() { if (swapped) { std::swap(h->work, h->fork_work); swapped = false; } h->stream = h->base; }
         ~ForkGuard() { leave(); (void)join_forks(h); }
     } guard{h};
     // (not in a map-range pass: its slices read their record count back, and measured at full size the kernels of two such
@@ -1308,20 +1341,14 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
         const uint64_t b = std::min(kmers, a + slice);
         int rc = reserve(h, b - a, b - a);
         if (rc) return rc;
-        const uint64_t sub_off = a ? a - 1 : 0;
-        const uint64_t sub_len = std::min(len, b + h->k) - sub_off;
-        const EmitRange er{a - sub_off, b - sub_off};
-        const uint8_t* ab; uint64_t lead;
-        const uint16_t* pinv = nullptr;
-        if (d_inv) { ab = (const uint8_t*)(reinterpret_cast<const uint32_t*>(d_bases) + sub_off / 16); pinv = d_inv + sub_off / 16; lead = sub_off % 16; }
-        else aligned_view(d_bases + sub_off, &ab, &lead);
+        const SliceView v = slice_view(d_bases, d_inv, len, h->k, a, b);
         // a table pass streams the whole table (2 x 16 B per slot) on top of ~37 B per record; the atomic path costs
         // ~95 ps per record whatever the table size (~480 B at the part's streaming rate): partition unless the table
         // is more than ~200 B per record the pass will apply -- this slice, plus what is pending already, times the
         // slices of this size the arena can still take (at most 8: the caller may read the table any time)
         double pass_records = (double)(b - a);
         if (h->pend_budget != 0) {
-            const double per_set = (double)set_bytes(b - a, FMT_PACK8, h->n_regions);
+            const double per_set = (double)set_bytes(b - a, FMT_PACK8, h->n_regions).total;
             const double room = h->arena ? (double)h->arena_bytes : 4.0 * (double)h->n_slots() * sizeof(Slot);
             pass_records = (double)h->pend_records + (double)(b - a) * std::max(1.0, std::min(8.0, room / per_set));
         }
@@ -1335,11 +1362,11 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
         if (part) {
             if (forked) {
                 const int w = (int)(slice_no & 1);
-                if (w == 1) { std::swap(h->part, h->fork_part[1]); std::swap(h->part_bytes, h->fork_part_bytes[1]); std::swap(h->part2, h->fork_part2); guard.swapped = true; }
+                if (w == 1) { std::swap(h->work, h->fork_work); guard.swapped = true; }
                 h->stream = h->fork_stream[w];
                 h->fork_busy[w] = true;
             }
-            rc = count_partitioned(h, ab, lead, sub_len, er, pinv);
+            rc = count_partitioned(h, v.ab, v.lead, v.len, v.er, v.pinv);
             if (forked) h->fork_busy[slice_no & 1] = true;            // (a table pass inside joined the stream; what followed has not been joined)
             guard.leave();
             if (rc) return rc;
@@ -1350,8 +1377,8 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
         filt.filt_lo = h->filt_lo; filt.filt_hi = h->filt_hi;
         materialize(h);
         h->table_empty = false;
-        hipLaunchKernelGGL(k_count_direct, dim3(grid_for(h, n_tiles_of(lead, sub_len), 1, 32)), dim3(TILE_THREADS), 0, h->stream,
-                           h->view(), ab, lead, sub_len, h->k, er, filt, pinv);
+        hipLaunchKernelGGL(k_count_direct, dim3(grid_for(h, n_tiles_of(v.lead, v.len), 1, 32)), dim3(TILE_THREADS), 0, h->stream,
+                           h->view(), v.ab, v.lead, v.len, h->k, v.er, filt, v.pinv);
         HIPC(hipGetLastError());
     }
     return KQ_OK;
@@ -1419,12 +1446,12 @@ static int ingest_begin(kq_handle* h, size_t bytes, uint64_t* ticket, int* slot,
     h->in_bad[t % kq_handle::IN_TICKETS] = 0;
     // the slot's previous reader must be done before it is overwritten (copy stream waits; the host does not)
     if (t >= (uint64_t)kq_handle::IN_SLOTS) HIPC(hipStreamWaitEvent(h->copy_stream, h->in_consumed[s], 0));
-    if (h->in_bytes[s] < bytes + 64) {
+    if (h->in_buf[s].bytes < bytes + 64) {
         // growing a slot: nothing may still read the old buffer
-        if (h->in_buf[s]) { HIPC(hipStreamSynchronize(h->copy_stream)); HIPC(hipStreamSynchronize(h->stream)); HIPC(hipFree(h->in_buf[s])); h->in_buf[s] = nullptr; h->in_bytes[s] = 0; }
+        if (h->in_buf[s].p) { HIPC(hipStreamSynchronize(h->copy_stream)); HIPC(hipStreamSynchronize(h->stream)); HIPC(hipFree(h->in_buf[s].p)); h->in_buf[s] = DevBuf(); }
         const size_t want = bytes + bytes / 4 + 4096;
-        HIPC(hipMalloc(&h->in_buf[s], want));
-        h->in_bytes[s] = want;
+        HIPC(hipMalloc(&h->in_buf[s].p, want));
+        h->in_buf[s].bytes = want;
     }
     return KQ_OK;
 }
@@ -1438,7 +1465,7 @@ static int ingest_async(kq_handle* h, const void* a, size_t a_bytes, const void*
     int s = 0; hipEvent_t copied;
     int rc = ingest_begin(h, bytes, ticket, &s, &copied);
     if (rc) return rc;
-    char* d = (char*)h->in_buf[s];
+    char* d = (char*)h->in_buf[s].p;
     if (a_bytes) HIPC(hipMemcpyAsync(d, a, a_bytes, hipMemcpyHostToDevice, h->copy_stream));
     if (b_bytes) HIPC(hipMemcpyAsync(d + b_off, b, b_bytes, hipMemcpyHostToDevice, h->copy_stream));
     HIPC(hipEventRecord(copied, h->copy_stream));
@@ -1489,7 +1516,7 @@ static uint64_t fx_units_of(const char* d_text, uint64_t len) { return (((uintpt
 static int fx_prepare(kq_handle* h, uint64_t n_units) {
     if (!h->fx_res) HIPC(hipMalloc((void**)&h->fx_res, sizeof(FxResult)));
     if (!h->fx_res_host) HIPC(hipHostMalloc((void**)&h->fx_res_host, sizeof(FxResult), hipHostMallocDefault));
-    return ensure_buf(&h->fx_units, &h->fx_units_bytes, (size_t)n_units * sizeof(FxUnit));
+    return ensure_buf(h->fx_units, (size_t)n_units * sizeof(FxUnit));
 }
 // summaries + scan on `st` (len > 0): the units hold every unit's output offset and incoming state, fx_res the total
 static void fx_scan(kq_handle* h, hipStream_t st, const char* d_text, uint64_t len, int format) {
@@ -1497,7 +1524,7 @@ static void fx_scan(kq_handle* h, hipStream_t st, const char* d_text, uint64_t l
     aligned_view(d_text, &ab, &lead);
     const uint64_t n_units = fx_units_of(d_text, len);
     const dim3 grid((unsigned)((n_units + FX_THREADS / 64 - 1) / (FX_THREADS / 64)));
-    FxUnit* units = (FxUnit*)h->fx_units;
+    FxUnit* units = (FxUnit*)h->fx_units.p;
     if (format == KQ_FASTX_FASTQ) {
         hipLaunchKernelGGL((k_fx_summary<FX_FASTQ>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, units);
         hipLaunchKernelGGL((k_fx_scan<FX_FASTQ>), dim3(1), dim3(FX_SCAN_THREADS), 0, st, ab, lead, units, n_units, h->fx_res);
@@ -1512,8 +1539,8 @@ static void fx_apply(kq_handle* h, hipStream_t st, const char* d_text, uint64_t 
     aligned_view(d_text, &ab, &lead);
     const uint64_t n_units = fx_units_of(d_text, len);
     const dim3 grid((unsigned)((n_units + FX_THREADS / 64 - 1) / (FX_THREADS / 64)));
-    if (format == KQ_FASTX_FASTQ) hipLaunchKernelGGL((k_fx_apply<FX_FASTQ>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, (const FxUnit*)h->fx_units, (uint8_t*)d_out, h->fx_res);
-    else hipLaunchKernelGGL((k_fx_apply<FX_FASTA>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, (const FxUnit*)h->fx_units, (uint8_t*)d_out, h->fx_res);
+    if (format == KQ_FASTX_FASTQ) hipLaunchKernelGGL((k_fx_apply<FX_FASTQ>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, (const FxUnit*)h->fx_units.p, (uint8_t*)d_out, h->fx_res);
+    else hipLaunchKernelGGL((k_fx_apply<FX_FASTA>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, (const FxUnit*)h->fx_units.p, (uint8_t*)d_out, h->fx_res);
 }
 static int fx_read_result(kq_handle* h, hipStream_t st) {
     HIPC(hipGetLastError());
@@ -1555,17 +1582,17 @@ int kq_count_fastx_dev(kq_handle* h, const char* d_text, uint64_t len, int forma
     if (!len) return KQ_OK;
     HIPC(hipSetDevice(h->device));
     rc = fx_prepare(h, fx_units_of(d_text, len)); if (rc) return rc;
-    if (h->fx_out_bytes < len + 64) {
+    if (h->fx_out.bytes < len + 64) {
         HIPC(hipStreamSynchronize(h->stream));             // (an earlier count may still read the old buffer)
-        rc = ensure_buf(&h->fx_out, &h->fx_out_bytes, len + 64); if (rc) return rc;
+        rc = ensure_buf(h->fx_out, len + 64); if (rc) return rc;
     }
     fx_scan(h, h->stream, d_text, len, format);
-    fx_apply(h, h->stream, d_text, len, format, (char*)h->fx_out);
+    fx_apply(h, h->stream, d_text, len, format, (char*)h->fx_out.p);
     // the count path plans its slices and scratch from the batch size on the host: one 16-byte read per call
     rc = fx_read_result(h, h->stream); if (rc) return rc;
     if (h->fx_res_host->bad) { h->fx_bad = format; return KQ_OK; }       // not counted; kq_sync reports it
     HistCacheOff guard(h);
-    return count_seq_dev(h, (const char*)h->fx_out, nullptr, h->fx_res_host->n_bases);
+    return count_seq_dev(h, (const char*)h->fx_out.p, nullptr, h->fx_res_host->n_bases);
 }
 
 int kq_count_fastx_async(kq_handle* h, const char* text, uint64_t len, int format, uint64_t* ticket) {
@@ -1577,18 +1604,18 @@ int kq_count_fastx_async(kq_handle* h, const char* text, uint64_t len, int forma
     std::lock_guard<std::mutex> lock(h->in_m);
     int s = 0; hipEvent_t copied;
     rc = ingest_begin(h, len, ticket, &s, &copied); if (rc) return rc;
-    if (h->in_cmp_bytes[s] < len + 64) {
-        if (h->in_cmp[s]) { HIPC(hipStreamSynchronize(h->copy_stream)); HIPC(hipStreamSynchronize(h->stream)); }
-        rc = ensure_buf(&h->in_cmp[s], &h->in_cmp_bytes[s], len + 64); if (rc) return rc;
+    if (h->in_cmp[s].bytes < len + 64) {
+        if (h->in_cmp[s].p) { HIPC(hipStreamSynchronize(h->copy_stream)); HIPC(hipStreamSynchronize(h->stream)); }
+        rc = ensure_buf(h->in_cmp[s], len + 64); if (rc) return rc;
     }
-    rc = fx_prepare(h, fx_units_of((const char*)h->in_buf[s], len)); if (rc) return rc;
+    rc = fx_prepare(h, fx_units_of((const char*)h->in_buf[s].p, len)); if (rc) return rc;
     // copy and parse on the copy stream: beside the counting of earlier batches.  The call waits for ITS OWN copy and parse
     // (the batch size plans the count on the host), never for the counting of earlier batches unless the ring is full
-    char* d = (char*)h->in_buf[s];
+    char* d = (char*)h->in_buf[s].p;
     HIPC(hipMemcpyAsync(d, text, len, hipMemcpyHostToDevice, h->copy_stream));
     HIPC(hipEventRecord(copied, h->copy_stream));
     fx_scan(h, h->copy_stream, d, len, format);
-    fx_apply(h, h->copy_stream, d, len, format, (char*)h->in_cmp[s]);
+    fx_apply(h, h->copy_stream, d, len, format, (char*)h->in_cmp[s].p);
     rc = fx_read_result(h, h->copy_stream); if (rc) return rc;
     if (h->fx_res_host->bad) {
         h->in_bad[*ticket % kq_handle::IN_TICKETS] = (uint8_t)format;
@@ -1596,7 +1623,7 @@ int kq_count_fastx_async(kq_handle* h, const char* text, uint64_t len, int forma
         rc = KQ_OK;
     } else {
         HistCacheOff guard(h);
-        rc = count_seq_dev(h, (const char*)h->in_cmp[s], nullptr, h->fx_res_host->n_bases);
+        rc = count_seq_dev(h, (const char*)h->in_cmp[s].p, nullptr, h->fx_res_host->n_bases);
     }
     HIPC(hipEventRecord(h->in_consumed[s], h->stream));
     return rc;
@@ -1607,9 +1634,9 @@ static int emit_ordered(kq_handle* h, const char* d_bases, uint64_t len, uint64_
     const uint8_t* ab; uint64_t lead;
     aligned_view(d_bases, &ab, &lead);
     const uint64_t nt = n_tiles_of(lead, len);
-    int rc = ensure_buf(&h->scratch, &h->scratch_bytes, (nt + 2) * sizeof(unsigned long long));
+    int rc = ensure_buf(h->scratch, (nt + 2) * sizeof(unsigned long long));
     if (rc) return rc;
-    unsigned long long* tile_counts = (unsigned long long*)h->scratch;
+    unsigned long long* tile_counts = (unsigned long long*)h->scratch.p;
     unsigned long long* total = tile_counts + nt;
     int grid = grid_for(h, nt, 1);
     hipLaunchKernelGGL(k_emit_count, dim3(grid), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, tile_counts);
@@ -1654,6 +1681,29 @@ int kq_emit_records(kq_handle* h, const char* bases, uint64_t len, uint64_t* key
     return rc;
 }
 
+// owner split of a resident batch (multi-GPU staging): records grouped by owner part in d_recs; d_edges != nullptr: WIDE
+// records (raw key + reference edge byte), else packed 8-byte records
+static int owner_split(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint8_t* d_edges, uint64_t* part_counts) {
+    const uint8_t* ab; uint64_t lead;
+    aligned_view(d_bases, &ab, &lead);
+    PartPlan p;
+    // up to 256 bins in all: owner part x sub-bin by lane (the order inside a part is unspecified anyway)
+    uint32_t sb = 0;
+    while (((uint32_t)n_parts << (sb + 1)) <= 256u && sb < 5) ++sb;
+    const uint32_t bins = (uint32_t)n_parts << sb;
+    int rc = plan_alloc(h, &p, 0, n_tiles_of(lead, len), bins);
+    if (rc) return rc;
+    PartCfg cfg = p.cfg;
+    cfg.mode = 1; cfg.n_coarse = bins; cfg.owner_sub = sb;
+    if (d_edges) cfg.raw_out = 1;
+    run_p1(h, &p, cfg, ab, lead, len, EmitRange{0, ~0ull}, d_recs, d_edges, d_edges ? AUX_EDGE_BYTE : AUX_IDX6);
+    std::vector<unsigned long long> off((size_t)bins + 1);
+    HIPC(hipMemcpyAsync(off.data(), p.seg_off, off.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPC(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n_parts; ++i) part_counts[i] = off[((size_t)i + 1) << sb] - off[(size_t)i << sb];
+    return KQ_OK;
+}
+
 int kq_emit_partitioned_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_keys, uint8_t* d_edges,
                             uint64_t cap, uint64_t* part_counts) {
     if (!h || !part_counts || n_parts < 1 || n_parts > h->map_count || n_parts >= NB_MAX || (!d_bases && len))
@@ -1664,23 +1714,7 @@ int kq_emit_partitioned_dev(kq_handle* h, const char* d_bases, uint64_t len, int
     if (len - h->k + 1 >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "an owner split handles fewer than 2^32 k-mer starts per call (got %llu): cut the batch", (unsigned long long)(len - h->k + 1));
     if (cap < len - h->k + 1 || !d_keys || !d_edges) return fail(KQ_ERR_CAPACITY, "record buffer too small: need room for %llu records",
                                                                   (unsigned long long)(len - h->k + 1));
-    const uint8_t* ab; uint64_t lead;
-    aligned_view(d_bases, &ab, &lead);
-    PartPlan p;
-    uint32_t sb = 0;                                             // owner part x sub-bin by lane, see kq_emit_packed_dev
-    while (((uint32_t)n_parts << (sb + 1)) <= 256u && sb < 5) ++sb;
-    const uint32_t bins = (uint32_t)n_parts << sb;
-    int rc = plan_alloc(h, &p, 0, n_tiles_of(lead, len), bins);
-    if (rc) return rc;
-    PartCfg cfg = p.cfg;
-    cfg.mode = 1; cfg.n_coarse = bins; cfg.owner_sub = sb;
-    cfg.raw_out = 1;
-    run_p1(h, &p, cfg, ab, lead, len, EmitRange{0, ~0ull}, d_keys, d_edges, AUX_EDGE_BYTE);      // WIDE records: key + reference edge byte
-    std::vector<unsigned long long> off((size_t)bins + 1);
-    HIPC(hipMemcpyAsync(off.data(), p.seg_off, off.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPC(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n_parts; ++i) part_counts[i] = off[((size_t)i + 1) << sb] - off[(size_t)i << sb];
-    return KQ_OK;
+    return owner_split(h, d_bases, len, n_parts, d_keys, d_edges, part_counts);
 }
 
 int kq_emit_packed_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint64_t cap,
@@ -1694,23 +1728,7 @@ int kq_emit_packed_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_pa
     if (len - h->k + 1 >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "an owner split handles fewer than 2^32 k-mer starts per call (got %llu): cut the batch", (unsigned long long)(len - h->k + 1));
     if (cap < len - h->k + 1 || !d_recs) return fail(KQ_ERR_CAPACITY, "record buffer too small: need room for %llu records",
                                                        (unsigned long long)(len - h->k + 1));
-    const uint8_t* ab; uint64_t lead;
-    aligned_view(d_bases, &ab, &lead);
-    PartPlan p;
-    // up to 256 bins in all: owner part x sub-bin by lane (the order inside a part is unspecified anyway)
-    uint32_t sb = 0;
-    while (((uint32_t)n_parts << (sb + 1)) <= 256u && sb < 5) ++sb;
-    const uint32_t bins = (uint32_t)n_parts << sb;
-    int rc = plan_alloc(h, &p, 0, n_tiles_of(lead, len), bins);
-    if (rc) return rc;
-    PartCfg cfg = p.cfg;
-    cfg.mode = 1; cfg.n_coarse = bins; cfg.owner_sub = sb;
-    run_p1(h, &p, cfg, ab, lead, len, EmitRange{0, ~0ull}, d_recs, nullptr, AUX_IDX6);
-    std::vector<unsigned long long> off((size_t)bins + 1);
-    HIPC(hipMemcpyAsync(off.data(), p.seg_off, off.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPC(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n_parts; ++i) part_counts[i] = off[((size_t)i + 1) << sb] - off[(size_t)i << sb];
-    return KQ_OK;
+    return owner_split(h, d_bases, len, n_parts, d_recs, nullptr, part_counts);
 }
 
 // ---- multi-GPU exchange of 5-byte records (k <= 21) -------------------------------------------------
@@ -1786,41 +1804,19 @@ int kq_insert_sharded_dev(kq_handle* h, const uint32_t* d_recs, const uint8_t* d
     if (rc) return rc;
     if (p.fmt != FMT_NARROW) return fail(KQ_ERR_INVALID, "the table is too small for 5-byte records (fewer than 2048 regions): use kq_insert_packed_dev");
     // segment table of the received array (peer-major runs) in logical order (bucket-major)
-    rc = ensure_buf(&h->scratch, &h->scratch_bytes, (size_t)(3 * (n_in + 2)) * 8);
+    rc = ensure_buf(h->scratch, (size_t)(3 * (n_in + 2)) * 8);
     if (rc) return rc;
-    unsigned long long* start = (unsigned long long*)h->scratch;
+    unsigned long long* start = (unsigned long long*)h->scratch.p;
     unsigned long long* seg_lo = start + n_in + 2;
     unsigned long long* seg_hi = seg_lo + n_in + 2;
     HIPC(hipMemcpyAsync(start, d_bucket_counts, (size_t)n_in * 8, hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, h->stream, start, (uint64_t)n_in, start + n_in);
     hipLaunchKernelGGL(k_sharded_segments, dim3((n_in + 255) / 256), dim3(256), 0, h->stream, start, (const unsigned long long*)d_bucket_counts, (uint32_t)n_peers, seg_lo, seg_hi);
-    P3Set set; bool in_arena = false;
-    const bool tight = tight_ok(h, p);
-    rc = arena_take(h, p.n_max, tight ? FMT_TIGHT : p.fmt, p.R, &set, &in_arena); if (rc) return rc;
-    const uint32_t sb = p.cfg.sub_bits;
-    uint64_t* fin = in_arena ? const_cast<uint64_t*>(set.recs) : p.recs2;
-    uint8_t* fin_aux = tight ? nullptr : in_arena ? const_cast<uint8_t*>(set.aux) : p.aux2;
-    unsigned long long* fin_base = in_arena ? const_cast<unsigned long long*>(set.base) : p.group_base;
-    unsigned long long* own_seg_off = p.seg_off;
-    LevelCfg first = level_narrow(p.cfg, sb, sb != 0);
-    first.n_seg = n_in; first.spb = (uint32_t)n_peers;
-    if (tight && sb == 0) first.rstart = h->rstart;               // it is the last level as well
-    p.seg_off = seg_lo;                                           // the first level reads the received runs
-    if (sb == 0) {
-        run_level(h, &p, first, (const uint64_t*)d_recs, d_aux, fin, fin_aux, fin_base, seg_hi);
-        p.seg_off = own_seg_off;
-    } else {
-        run_level(h, &p, first, (const uint64_t*)d_recs, d_aux, p.recs1, p.aux1, nullptr, seg_hi);
-        p.seg_off = own_seg_off;
-        HIPC(hipMemcpyAsync(p.seg_off, p.group_base, (size_t)(((1u << NARROW_CBITS) << sb) + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
-        if (!in_arena) { fin = p.recs2; fin_aux = tight ? nullptr : p.aux2; }
-        LevelCfg last = level_narrow(p.cfg, sb, false);
-        if (tight) last.rstart = h->rstart;
-        run_level(h, &p, last, p.recs1, p.aux1, fin, fin_aux, fin_base);
-    }
-    if (!in_arena) set = P3Set{fin, fin_aux, fin_base, p.n_max};
-    HIPC(hipGetLastError());
-    return pend_or_apply(h, set, tight ? FMT_TIGHT : FMT_NARROW, tight ? AUX_TIGHT : AUX_IDX6, in_arena);
+    Dest dst{p.fmt, AUX_IDX6};
+    rc = dest_take(h, p, p.n_max, &dst); if (rc) return rc;
+    // the first level reads the received runs
+    const LevelIn runs{(const uint64_t*)d_recs, d_aux, seg_lo, seg_hi, n_in, (uint32_t)n_peers};
+    return submit(h, sort_to_regions(h, &p, runs, dst), dst);
 }
 
 int kq_insert_packed_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n) {
@@ -1853,10 +1849,10 @@ int kq_insert_records(kq_handle* h, const uint64_t* keys, const uint8_t* edges, 
     if (!h || ((!keys || !edges) && n)) return fail(KQ_ERR_INVALID, "null argument");
     HIPC(hipSetDevice(h->device));
     if (!n) return KQ_OK;
-    int rc = ensure_buf(&h->stage, &h->stage_bytes, n * 9 + 64);
+    int rc = ensure_buf(h->stage, n * 9 + 64);
     if (rc) return rc;
-    uint64_t* dk = (uint64_t*)h->stage;
-    uint8_t* de = (uint8_t*)h->stage + n * 8;
+    uint64_t* dk = (uint64_t*)h->stage.p;
+    uint8_t* de = (uint8_t*)h->stage.p + n * 8;
     HIPC(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, h->stream));
     HIPC(hipMemcpyAsync(de, edges, n, hipMemcpyHostToDevice, h->stream));
     rc = kq_insert_records_dev(h, dk, de, n);
@@ -1869,12 +1865,12 @@ struct SummaryHost { SummaryOut so; std::vector<unsigned long long> small; std::
 static int run_summary(kq_handle* h, SummaryHost* r) {
     const uint64_t big_cap = h->hc_cap;     // cov >= 4096 implies a high-copy k-mer
     size_t need = sizeof(SummaryOut) + HIST_SMALL * sizeof(unsigned long long) + big_cap * sizeof(uint32_t);
-    int rc = ensure_buf(&h->scratch, &h->scratch_bytes, need);
+    int rc = ensure_buf(h->scratch, need);
     if (rc) return rc;
-    SummaryOut* d_so = (SummaryOut*)h->scratch;
+    SummaryOut* d_so = (SummaryOut*)h->scratch.p;
     unsigned long long* d_small = (unsigned long long*)(d_so + 1);
     uint32_t* d_big = (uint32_t*)(d_small + HIST_SMALL);
-    HIPC(hipMemsetAsync(h->scratch, 0, sizeof(SummaryOut) + HIST_SMALL * sizeof(unsigned long long), h->stream));
+    HIPC(hipMemsetAsync(h->scratch.p, 0, sizeof(SummaryOut) + HIST_SMALL * sizeof(unsigned long long), h->stream));
     SummaryOut init; memset(&init, 0, sizeof init); init.big_cap = big_cap;
     HIPC(hipMemcpyAsync(d_so, &init, sizeof init, hipMemcpyHostToDevice, h->stream));
     materialize(h);
@@ -1932,26 +1928,14 @@ int kq_histogram(kq_handle* h, uint64_t* cov, uint64_t* cnt, uint64_t cap, uint6
 static int lookup_partitioned(kq_handle* h, const uint8_t* ab, uint64_t lead, uint64_t len, EmitRange er, uint32_t cov_cutoff,
                               uint32_t map_lo, uint32_t map_hi, unsigned long long* d_counters) {
     PartPlan p;
-    PartCfg c0; plan_cfg(h, &c0, true);
-    int rc = plan_alloc(h, &p, len, n_tiles_of(lead, len), c0.n_coarse, true);
+    int rc = plan_sequence(h, &p, lead, len);
     if (rc) return rc;
-    if (h->k > PART_MAX_K && p.fmt != FMT_TOP8) p.fmt = FMT_WIDE;
-    const bool has_aux = p.fmt == FMT_WIDE || p.fmt == FMT_NARROW;
-    uint8_t* a1 = has_aux ? p.aux1 : nullptr;
-    uint8_t* a2 = has_aux ? p.aux2 : nullptr;
     p.cfg.filt_lo = map_lo; p.cfg.filt_hi = map_hi;               // the reference's range filter, src/kreeq.cpp:150
-    run_p1(h, &p, p.cfg, ab, lead, len, er, p.recs1, a1, AUX_IDX6);
-    const uint64_t* sorted = p.recs1; const uint8_t* sorted_aux = a1; const unsigned long long* base = p.seg_off;
-    if (p.fmt == FMT_NARROW || p.fmt == FMT_TOP8) {
-        run_narrow_levels(h, &p, &sorted, &sorted_aux);
-        base = p.group_base;
-    } else if (p.two_level) {
-        run_level(h, &p, level_coarse_to_regions(p.cfg), p.recs1, a1, p.recs2, a2);
-        sorted = p.recs2; sorted_aux = a2; base = p.group_base;
-    }
+    run_p1(h, &p, p.cfg, ab, lead, len, er, p.recs1, p.a1(), AUX_IDX6);
+    const P3Set set = sort_to_regions(h, &p, own_segments(p, p.recs1, p.a1(), p.cfg.n_coarse), Dest{p.fmt, AUX_IDX6});      // in the scratch, never tight
     const uint32_t rps = (p.fmt == FMT_NARROW || p.fmt == FMT_TOP8) ? (uint32_t)(p.R >> NARROW_CBITS) : 1u;
     const dim3 grid((unsigned)std::min<uint64_t>(p.R, 1u << 30)), block(P3_THREADS);
-#define KQ_LK(F) hipLaunchKernelGGL((k_lookup_regions<F>), grid, block, 0, h->stream, h->view(), sorted, sorted_aux, base, rps, cov_cutoff, d_counters)
+#define KQ_LK(F) hipLaunchKernelGGL((k_lookup_regions<F>), grid, block, 0, h->stream, h->view(), set.recs, set.aux, set.base, rps, cov_cutoff, d_counters)
     if (p.fmt == FMT_NARROW) KQ_LK(FMT_NARROW); else if (p.fmt == FMT_TOP8) KQ_LK(FMT_TOP8); else if (p.fmt == FMT_WIDE) KQ_LK(FMT_WIDE); else KQ_LK(FMT_PACK8);
 #undef KQ_LK
     HIPC(hipGetLastError());
@@ -1976,11 +1960,8 @@ int kq_lookup_sequence_dev(kq_handle* h, const char* d_bases, uint64_t len, uint
         (h->lookup_path == 2 || (kmers >= (1u << 20) && (double)h->n_slots() * sizeof(Slot) <= 64.0 * (double)std::min<uint64_t>(kmers, h->slice_kmers)))) {
         for (uint64_t a = 0; a < kmers; a += h->slice_kmers) {
             const uint64_t b = std::min(kmers, a + h->slice_kmers);
-            const uint64_t sub_off = a ? a - 1 : 0;
-            const uint64_t sub_len = std::min(len, b + h->k) - sub_off;
-            const uint8_t* sab; uint64_t slead;
-            aligned_view(d_bases + sub_off, &sab, &slead);
-            int rc = lookup_partitioned(h, sab, slead, sub_len, EmitRange{a - sub_off, b - sub_off}, cov_cutoff, map_lo, map_hi, (unsigned long long*)d_counters);
+            const SliceView v = slice_view(d_bases, nullptr, len, h->k, a, b);
+            int rc = lookup_partitioned(h, v.ab, v.lead, v.len, v.er, cov_cutoff, map_lo, map_hi, (unsigned long long*)d_counters);
             if (rc) return rc;
         }
         return KQ_OK;
@@ -2033,9 +2014,9 @@ int kq_lookup_keys(kq_handle* h, const uint64_t* keys, uint64_t n, kq_entry* out
     if (rc) return rc;
     materialize(h);
     // keys in, entries out: one scratch buffer (8 + 48 bytes per key)
-    rc = ensure_buf(&h->stage, &h->stage_bytes, (size_t)n * (sizeof(uint64_t) + sizeof(kq_entry)) + 64);
+    rc = ensure_buf(h->stage, (size_t)n * (sizeof(uint64_t) + sizeof(kq_entry)) + 64);
     if (rc) return rc;
-    uint64_t* d_keys = (uint64_t*)h->stage;
+    uint64_t* d_keys = (uint64_t*)h->stage.p;
     kq_entry* d_out = (kq_entry*)(d_keys + ((n + 1) & ~1ull));
     HIPC(hipMemcpyAsync(d_keys, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_lookup_keys, dim3(grid_for(h, n, 256)), dim3(256), 0, h->stream, h->view(), d_keys, n, d_out);
