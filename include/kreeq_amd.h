@@ -132,7 +132,15 @@ void* kq_get_stream(kq_handle* h);
  *                          split of the count path is the owner split of the exchange (kq_emit_sharded_dev /
  *                          kq_insert_sharded_dev).  k-mers of other buckets are ignored by every entry point: counts drop
  *                          them, lookups do not evaluate them (their sum over the shards is the whole answer, like the map
- *                          ranges of src/kreeq.cpp:150), export / summary see the window's k-mers. */
+ *                          ranges of src/kreeq.cpp:150), export / summary see the window's k-mers.
+ *                          (KQ_OPT_SHARD_WINDOW is its superset: the same for k <= 21, and k = 29..32 as well.)
+ *   KQ_OPT_SHARD_WINDOW    value = lo | hi << 16: KQ_OPT_BUCKET_WINDOW with every one of its rules (empty handle, 0 <= lo < hi <=
+ *                          256, an empty windowed table moves to a window of the same width without a new allocation, [0, 256)
+ *                          gives an ordinary table again), accepted for k <= 21 -- the same code path -- AND for k = 29..32,
+ *                          whose tables have the 256-bucket geometry at every size (a slot there stores the 56 hash bits below
+ *                          the bucket prefix; the prefix is implied by the slot's region of the whole geometry, windowed or not).
+ *                          The shard of kq_emit_sharded8_dev / kq_insert_sharded8_dev.  k = 22..28 is refused: those shards
+ *                          own map ranges (kq_emit_packed_dev). */
 /*   KQ_OPT_OVERLAP        1 (default): a count call that cuts its batch into several slices (KQ_OPT_SLICE_KMERS) runs the
  *                          partition stages of consecutive slices on two internal streams with a scratch set each (slice
  *                          j+1's scan beside slice j's split levels) and joins them with the handle's stream before it
@@ -150,7 +158,7 @@ void* kq_get_stream(kq_handle* h);
  *                          streamed formulation, which lost there) instead of k_lv_scatter, 4 = the level that writes tight records
  *                          with k_lv_scatter (round 2's) instead of k_lv_scatter_s.  Default 0. */
 enum { KQ_OPT_TRUST_CAPACITY = 1, KQ_OPT_COUNT_PATH = 2, KQ_OPT_SLICE_KMERS = 3, KQ_OPT_COUNT_MAP_RANGE = 4, KQ_OPT_PROFILE = 5,
-       KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13,
+       KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13, KQ_OPT_SHARD_WINDOW = 14,
        KQ_OPT_TEST_FAIL_PLAN = 100 /* failure-path tests only: the next partition plan of a count fails with KQ_ERR_NOMEM */ };
 int  kq_set_option(kq_handle* h, int option, int64_t value);
 int  kq_get_profile(kq_handle* h, char* buf, uint64_t cap);
@@ -278,6 +286,24 @@ int  kq_insert_packed_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n);
 int  kq_emit_sharded_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint32_t* d_recs, uint8_t* d_aux, uint64_t cap,
                          uint64_t* d_bucket_counts, uint64_t* part_counts);
 int  kq_insert_sharded_dev(kq_handle* h, const uint32_t* d_recs, const uint8_t* d_aux, uint64_t n, int n_peers, const uint64_t* d_bucket_counts);
+
+/* The same staging for k = 29..32 with 8-BYTE HASH-REMAINDER records: d_recs[i] (u64) = bits 8..63: the 56 bits of the k-mer's
+ * table hash below its 8-bit hash-prefix bucket, bits 0..5: its two edge indices, bits 6..7: zero -- the record format of the
+ * single-GPU count at these k, written by its first (bucket) split; opaque to the caller and stable within an ABI version
+ * like the other record formats.  A record and the bucket of the run it lies in are the whole k-mer.  Everything else is the
+ * contract of kq_emit_sharded_dev / kq_insert_sharded_dev with one array instead of two: parts are the bucket ranges
+ * [ceil(256 p / n_parts), ceil(256 (p + 1) / n_parts)), the output is bucket-sorted (every part one run), d_bucket_counts is
+ * [n_parts x 256] on the DEVICE, part_counts == NULL only enqueues; the sending handle needs no particular table (a window
+ * it may have is not applied: every bucket is emitted).  KQ_ERR_INVALID for k outside 29..32, n_parts outside 1..256 or null
+ * pointers, KQ_ERR_CAPACITY when cap < len - k + 1, fewer than 2^32 k-mer starts per call; len < k: all counts zero, KQ_OK.
+ * kq_insert_sharded8_dev takes the runs of all peers concatenated in peer order and d_bucket_counts = [n_peers x 256]
+ * (DEVICE, peer-major); the receiving handle is the window of its buckets (KQ_OPT_SHARD_WINDOW; with one part: an ordinary
+ * table) and must have >= 2048 regions (KQ_ERR_INVALID otherwise: smaller tables take kq_emit_partitioned_dev /
+ * kq_insert_records_dev); records of buckets outside its window are ignored.  Pending sets (KQ_OPT_PENDING_BYTES) and table
+ * growth work as for a count.  8 bytes per record in one all-to-all(v) instead of 9 in two. */
+int  kq_emit_sharded8_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint64_t cap,
+                          uint64_t* d_bucket_counts, uint64_t* part_counts);
+int  kq_insert_sharded8_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n, int n_peers, const uint64_t* d_bucket_counts);
 
 /* Hot loop 2 only (DBG::processBuffers :160-206) on explicit records. */
 int  kq_insert_records(kq_handle* h, const uint64_t* keys, const uint8_t* edges, uint64_t n);

@@ -15,7 +15,7 @@ DBGBASE_DTYPE = np.dtype([("fw", "<u4"), ("bw", "<u4"), ("cov", "<u4"), ("isFw",
 SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profile", "kq_set_stream", "kq_get_stream", "kq_sync", "kq_flush", "kq_get_info", "kq_last_error",
            "kq_abi_version", "kq_device_available", "kq_device_memory", "kq_count_batch", "kq_count_batch_dev", "kq_host_alloc", "kq_host_free", "kq_count_batch_async", "kq_host_wait", "kq_pack_bases", "kq_count_packed_dev", "kq_count_packed_async",
            "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_emit_records",
-           "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
+           "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
            "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_lookup_keys", "kq_branch_scan", "kq_merge", "kq_import", "kq_export"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
@@ -115,6 +115,8 @@ def load():
     L.kq_insert_packed_dev.argtypes = [vp, vp, u64]
     L.kq_emit_sharded_dev.argtypes = [vp, vp, u64, ci, vp, vp, u64, vp, vp]
     L.kq_insert_sharded_dev.argtypes = [vp, vp, vp, u64, ci, vp]
+    L.kq_emit_sharded8_dev.argtypes = [vp, vp, u64, ci, vp, u64, vp, vp]
+    L.kq_insert_sharded8_dev.argtypes = [vp, vp, u64, ci, vp]
     L.kq_insert_records.argtypes = [vp, vp, vp, u64]
     L.kq_insert_records_dev.argtypes = [vp, vp, vp, u64]
     L.kq_summary.argtypes = [vp, C.POINTER(Stats)]
@@ -191,7 +193,7 @@ class KreeqDB:
 
     def set_option(self, option, value):
         """option: 'trust_capacity' | 'count_path' ('auto'|'direct'|'partitioned') | 'slice_kmers' | 'count_map_range' ((lo, hi))"""
-        opt = {"trust_capacity": 1, "count_path": 2, "slice_kmers": 3, "count_map_range": 4, "profile": 5, "lookup_path": 6, "merge_path": 7, "narrow_mid": 8, "pending_bytes": 9, "bucket_window": 10, "overlap": 11, "count_map_passes": 12, "kernel_set": 13, "test_fail_plan": 100}[option]
+        opt = {"trust_capacity": 1, "count_path": 2, "slice_kmers": 3, "count_map_range": 4, "profile": 5, "lookup_path": 6, "merge_path": 7, "narrow_mid": 8, "pending_bytes": 9, "bucket_window": 10, "overlap": 11, "count_map_passes": 12, "kernel_set": 13, "shard_window": 14, "test_fail_plan": 100}[option]
         if option == "count_map_range":
             value = int(value[0]) | (int(value[1]) << 16)
         if option in ("count_path", "lookup_path", "merge_path"):
@@ -299,6 +301,16 @@ class KreeqDB:
 
     def insert_sharded_dev(self, recs_ptr, aux_ptr, n, n_peers, bucket_counts_ptr):
         _check(load().kq_insert_sharded_dev(self._h, C.c_void_p(recs_ptr), C.c_void_p(aux_ptr), n, n_peers, C.c_void_p(bucket_counts_ptr)))
+
+    def emit_sharded8_dev(self, bases_ptr, n, n_parts, recs_ptr, cap, bucket_counts_ptr, sync=True):
+        """k = 29..32: bucket-sorted 8-byte hash-remainder records (one u64 array); sync=False only enqueues and returns None"""
+        counts = np.zeros(n_parts, dtype=np.uint64) if sync else None
+        _check(load().kq_emit_sharded8_dev(self._h, C.c_void_p(bases_ptr), n, n_parts, C.c_void_p(recs_ptr), cap,
+                                           C.c_void_p(bucket_counts_ptr), _p(counts)))
+        return counts
+
+    def insert_sharded8_dev(self, recs_ptr, n, n_peers, bucket_counts_ptr):
+        _check(load().kq_insert_sharded8_dev(self._h, C.c_void_p(recs_ptr), n, n_peers, C.c_void_p(bucket_counts_ptr)))
 
     def insert_records(self, keys, edges):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)

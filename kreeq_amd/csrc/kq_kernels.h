@@ -246,6 +246,8 @@ __global__ __launch_bounds__(TILE_THREADS, (NBC <= 512 && FMT != FMT_WIDE) ? 3 :
 // time), ONE split over the TPR x 4032 starts: runs of a bin TPR times as long at the same number of waves per CU.
 // TOP8 (k = 29..32): the record is a whole u64 (top8_rec), so its bin travels in a second LDS array (u16) and the stage takes 40 KiB:
 // three workgroups per CU, one tile per round.  Replaces k_p1_scatter<FMT_TOP8> (32 spilled registers at k = 31).
+// BINMODE 6 with TOP8 (a windowed k = 29..32 table): the bin is decided first, a k-mer of a foreign bucket takes bin NB and is never
+// placed -- same LDS, no more registers than BINMODE 2.
 template <int BINMODE, int KC, int TPR, bool TOP8 = false>
 __global__ __launch_bounds__(TILE_THREADS * TPR, TOP8 ? 3 : 4 / TPR) void k_p1_scatter_s(const uint8_t* __restrict__ ab, uint64_t lead, uint64_t len, int k_arg,
                                                              PartCfg cfg, EmitRange er, const unsigned long long* __restrict__ m1,

@@ -125,7 +125,7 @@ struct kq_handle {
     int n_cu = 256;
     Slot* slots = nullptr;
     uint64_t n_regions = 0;          // of the table's geometry (the scale of the hash -> region map)
-    // window (multi-GPU shards, KQ_OPT_BUCKET_WINDOW): only the regions of the hash-prefix buckets [win_lo, win_hi) are
+    // window (multi-GPU shards, KQ_OPT_BUCKET_WINDOW / KQ_OPT_SHARD_WINDOW): only the regions of the hash-prefix buckets [win_lo, win_hi) are
     // allocated; `slots` is the allocation, view().slots the address region 0 would have
     uint32_t win_lo = 0, win_hi = 256;
     bool windowed = false;
@@ -476,10 +476,15 @@ static uint64_t round_regions(uint64_t regions, int k) {
 }
 // KQ_OPT_BUCKET_WINDOW: the (empty) table becomes the window [lo, hi) of the 256 hash-prefix buckets of a geometry that is
 // 256 / (hi - lo) times larger: the memory stays what kq_create sized, the handle then holds -- and answers for -- only
-// the k-mers of those buckets (a multi-GPU shard; kq_insert_sharded_dev brings them)
-static int set_window(kq_handle* h, uint32_t lo, uint32_t hi) {
+// the k-mers of those buckets (a multi-GPU shard; kq_insert_sharded_dev / kq_insert_sharded8_dev bring them).
+// `shard` (KQ_OPT_SHARD_WINDOW): also for k >= HI_K, whose tables have the bucket geometry at every size and whose slots take
+// their top 8 hash bits from the region -- the VIRTUAL region (view().slots is the address region 0 would have), so a window
+// changes nothing in slot_hash / slot_hash_at
+static int set_window(kq_handle* h, uint32_t lo, uint32_t hi, bool shard = false) {
     if (lo >= hi || hi > 256) return fail(KQ_ERR_INVALID, "bucket window [%u, %u) is not a range of the 256 hash-prefix buckets", lo, hi);
-    if (h->k > (int)NARROW_MAX_K) return fail(KQ_ERR_INVALID, "bucket windows need k <= %u (5-byte records)", NARROW_MAX_K);
+    if (shard && h->k > (int)NARROW_MAX_K && h->k < HI_K)
+        return fail(KQ_ERR_INVALID, "shard windows need k <= %u (5-byte records) or k >= %d (8-byte hash-remainder records); k = %u..%d shards own map ranges", NARROW_MAX_K, HI_K, NARROW_MAX_K + 1, HI_K - 1);
+    if (!shard && h->k > (int)NARROW_MAX_K) return fail(KQ_ERR_INVALID, "bucket windows need k <= %u (5-byte records)", NARROW_MAX_K);
     if (!h->table_empty || h->n_pend || h->kmers_bound) return fail(KQ_ERR_INVALID, "the bucket window is chosen before anything is counted");
     // an empty windowed table moves to another window of the same width without a new allocation (bucket-range passes of one
     // GPU: count the buckets [0, 128), clear, count [128, 256) into the same memory)
@@ -651,6 +656,9 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
         case KQ_OPT_BUCKET_WINDOW:
             HIPC(hipSetDevice(h->device));
             return set_window(h, (uint32_t)(value & 0xFFFF), (uint32_t)((value >> 16) & 0xFFFF));
+        case KQ_OPT_SHARD_WINDOW:
+            HIPC(hipSetDevice(h->device));
+            return set_window(h, (uint32_t)(value & 0xFFFF), (uint32_t)((value >> 16) & 0xFFFF), true);
         case KQ_OPT_SLICE_KMERS:
             if (value < 1) return fail(KQ_ERR_INVALID, "KQ_OPT_SLICE_KMERS must be positive");
             h->slice_kmers = (uint64_t)value; h->slice_user = true; return KQ_OK;
@@ -826,7 +834,7 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     const bool plain = cfg.mode == 0 && cfg.filt_lo == 0 && cfg.filt_hi == cfg.map_count;
     const bool owner_plain = cfg.mode == 1 && cfg.map_mask != 0 && cfg.filt_lo == 0 && cfg.filt_hi == cfg.map_count;   // multi-GPU owner split
     const bool narrow_filt = cfg.mode == 0 && cfg.narrow && !plain && cfg.map_mask != 0 && h->k <= (int)NARROW_MAX_K;   // map-range pass on a bucketed table
-    const bool narrow_win = plain && cfg.narrow && h->k <= (int)NARROW_MAX_K && (cfg.win_lo != 0 || cfg.win_hi != (1u << NARROW_CBITS));   // windowed table: own buckets only
+    const bool narrow_win = plain && cfg.narrow && (h->k <= (int)NARROW_MAX_K || h->k > PART_MAX_K) && (cfg.win_lo != 0 || cfg.win_hi != (1u << NARROW_CBITS));   // windowed table: own buckets only
     const int binmode = owner_plain ? 3 : narrow_filt ? 4 : narrow_win ? 6 : !plain ? 0 : cfg.narrow ? 2 : 1;
     // KQ_OPT_COUNT_MAP_PASSES = n: this map-range pass is one of n over RESIDENT batches (the caller vouches that a batch keeps
     // its address and content between the passes).  The first pass that scans a slice counts for all n ranges in one histogram
@@ -867,7 +875,7 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
             PartCfg all = cfg;
             all.win_lo = 0; all.win_hi = 1u << NARROW_CBITS;
             if (h->k == 21) hipLaunchKernelGGL((k_p1_hist<2, 21>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
-            else hipLaunchKernelGGL((k_p1_hist<2, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
+            else hipLaunchKernelGGL((k_p1_hist<2, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);      // (any k: hash-remainder records too)
         });
         if (ent) {
             (void)hipMemcpyAsync(p->m1, ent->m1_all, block, hipMemcpyDeviceToDevice, h->stream);
@@ -878,7 +886,7 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     }
 #define KQ_P1H(B, K) hipLaunchKernelGGL((k_p1_hist<B, K>), dim3(p->g1 * P1_F), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, cfg, er, p->g1, p->m1, pinv)
     if (have_hist) { }
-    else if (binmode == 6) { if (h->k == 21) KQ_P1H(6, 21); else KQ_P1H(6, 0); }
+    else if (binmode == 6) { if (h->k == 21) KQ_P1H(6, 21); else if (h->k == 31) KQ_P1H(6, 31); else KQ_P1H(6, 0); }
     else if (binmode == 2) { if (h->k == 21) KQ_P1H(2, 21); else KQ_P1H(2, 0); }
     else if (binmode == 1) { if (h->k == 31) KQ_P1H(1, 31); else KQ_P1H(1, 0); }
     else if (binmode == 3) { if (h->k == 21) KQ_P1H(3, 21); else KQ_P1H(3, 0); }
@@ -892,7 +900,11 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
 #define KQ_P1S(W, N, B, K) hipLaunchKernelGGL((k_p1_scatter<W, N, B, K>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, cfg, er, p->m1, out, out_aux, aux_fmt, pinv)
 #define KQ_P1T(B, K) do { if (h->kernel_set & 1) KQ_P1S(FMT_TOP8, 512, B, K); else \
         hipLaunchKernelGGL((k_p1_scatter_s<B, K, 1, true>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, cfg, er, p->m1, (uint32_t*)out, out_aux, pinv); } while (0)
-    if (cfg.narrow && h->k > PART_MAX_K) { if (plain && h->k == 31) KQ_P1T(2, 31); else if (plain) KQ_P1T(2, 0); else KQ_P1T(0, 0); }
+    // hash-remainder records (k = 29..32); a windowed table drops the k-mers of foreign buckets here, like the narrow scatter below
+    if (cfg.narrow && h->k > PART_MAX_K) {
+        if (narrow_win) { if (h->k == 31) KQ_P1T(6, 31); else KQ_P1T(6, 0); }
+        else if (plain && h->k == 31) KQ_P1T(2, 31); else if (plain) KQ_P1T(2, 0); else KQ_P1T(0, 0);
+    }
     // narrow records: the streamed scatter (k_p1_scatter_s); a pass that keeps every k-mer splits two tiles per round, a filtered one one
 #define KQ_P1N(B, K, T) do { if (h->kernel_set & 1) KQ_P1S(FMT_NARROW, 512, B, K); else \
         hipLaunchKernelGGL((k_p1_scatter_s<B, K, T>), dim3(p->g1), dim3(TILE_THREADS * T), 0, h->stream, ab, lead, len, h->k, cfg, er, p->m1, (uint32_t*)out, out_aux, pinv); } while (0)
@@ -1816,6 +1828,78 @@ int kq_insert_sharded_dev(kq_handle* h, const uint32_t* d_recs, const uint8_t* d
     rc = dest_take(h, p, p.n_max, &dst); if (rc) return rc;
     // the first level reads the received runs
     const LevelIn runs{(const uint64_t*)d_recs, d_aux, seg_lo, seg_hi, n_in, (uint32_t)n_peers};
+    return submit(h, sort_to_regions(h, &p, runs, dst), dst);
+}
+
+// ---- multi-GPU exchange of 8-byte hash-remainder records (k = 29..32) -------------------------------
+// The same glue for FMT_TOP8: a record plus its bucket is the whole k-mer (top8_hash), tables of k >= HI_K have the bucket
+// geometry at every size, so ownership by bucket range makes P1 the owner split here too.  One u64 array crosses the link
+// (the 9-byte path: u64 key + edge byte in two arrays, hashed again by the receiver), and the receiver's levels start from
+// the (peer, bucket) runs.  kq_emit_partitioned_dev / kq_insert_records_dev remain for tables below 2048 regions.
+int kq_emit_sharded8_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint64_t cap,
+                         uint64_t* d_bucket_counts, uint64_t* part_counts) {
+    if (!h || !d_bucket_counts || n_parts < 1 || n_parts > 256 || (!d_bases && len))
+        return fail(KQ_ERR_INVALID, "bad argument");
+    if (h->k <= PART_MAX_K) return fail(KQ_ERR_INVALID, "8-byte hash-remainder records need k >= %d (use kq_emit_sharded_dev or kq_emit_packed_dev)", HI_K);
+    HIPC(hipSetDevice(h->device));
+    for (int i = 0; part_counts && i < n_parts; ++i) part_counts[i] = 0;
+    const uint64_t n_groups = (uint64_t)n_parts << NARROW_CBITS;
+    HIPC(hipMemsetAsync(d_bucket_counts, 0, n_groups * 8, h->stream));
+    if (len < (uint64_t)h->k) { if (part_counts) HIPC(hipStreamSynchronize(h->stream)); return KQ_OK; }
+    if (len - h->k + 1 >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "a bucket split handles fewer than 2^32 k-mer starts per call (got %llu): cut the batch", (unsigned long long)(len - h->k + 1));
+    if (cap < len - h->k + 1 || !d_recs) return fail(KQ_ERR_CAPACITY, "record buffer too small: need room for %llu records", (unsigned long long)(len - h->k + 1));
+    const uint8_t* ab; uint64_t lead;
+    aligned_view(d_bases, &ab, &lead);
+    PartPlan p;
+    int rc = plan_alloc(h, &p, 0, n_tiles_of(lead, len), 1u << NARROW_CBITS, true, n_groups);      // (P1 writes into the caller's buffer: no record scratch)
+    if (rc) return rc;
+    // bucket = top 8 hash bits whatever this rank's table looks like (plan_cfg leaves the window of the sending handle out:
+    // every bucket is emitted), and every part is a range of buckets
+    PartCfg cfg = p.cfg;
+    cfg.mode = 0; cfg.narrow = 1; cfg.n_coarse = 1u << NARROW_CBITS; cfg.sub_bits = 0; if (cfg.g_shift == 0) cfg.g_shift = 1;
+    cfg.filt_lo = 0; cfg.filt_hi = cfg.map_count;
+    run_p1(h, &p, cfg, ab, lead, len, EmitRange{0, ~0ull}, d_recs, nullptr, AUX_IDX6);
+    hipLaunchKernelGGL(k_bucket_meta, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, h->stream, p.seg_off, (uint32_t)n_parts, (unsigned long long*)d_bucket_counts);
+    HIPC(hipGetLastError());
+    if (!part_counts) return KQ_OK;               // asynchronous: the caller takes the part sizes from the rows of d_bucket_counts
+    std::vector<unsigned long long> off((size_t)(1u << NARROW_CBITS) + 1);
+    HIPC(hipMemcpyAsync(off.data(), p.seg_off, off.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPC(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n_parts; ++i) part_counts[i] = off[part_first_bucket(i + 1, n_parts)] - off[part_first_bucket(i, n_parts)];
+    return KQ_OK;
+}
+
+int kq_insert_sharded8_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n, int n_peers, const uint64_t* d_bucket_counts) {
+    if (!h || (!d_recs && n) || !d_bucket_counts || n_peers < 1 || n_peers > 256) return fail(KQ_ERR_INVALID, "bad argument");
+    if (h->k <= PART_MAX_K) return fail(KQ_ERR_INVALID, "8-byte hash-remainder records need k >= %d (use kq_insert_sharded_dev or kq_insert_packed_dev)", HI_K);
+    HIPC(hipSetDevice(h->device));
+    if (!n) return KQ_OK;
+    if (n >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "a partition pass handles fewer than 2^32 records (got %llu)", (unsigned long long)n);
+    {   // the format of the plan the table allows, before anything is reserved or grown for records it cannot take
+        PartCfg c; plan_cfg(h, &c, true);
+        if (!c.narrow) return fail(KQ_ERR_INVALID, "the table has no hash-prefix bucket split for 8-byte hash-remainder records (fewer than 2048 regions): use kq_insert_records_dev");
+    }
+    int rc = reserve(h, n, n);
+    if (rc) return rc;
+    const uint32_t n_in = (uint32_t)n_peers << NARROW_CBITS;      // input segments: one run per (bucket, peer)
+    PartPlan p;
+    rc = plan_alloc(h, &p, n, 0, 1, true, n_in);
+    if (rc) return rc;
+    if (p.fmt != FMT_TOP8) return fail(KQ_ERR_INVALID, "the table has no hash-prefix bucket split for 8-byte hash-remainder records: use kq_insert_records_dev");
+    // segment table of the received array (peer-major runs) in logical order (bucket-major)
+    rc = ensure_buf(h->scratch, (size_t)(3 * (n_in + 2)) * 8);
+    if (rc) return rc;
+    unsigned long long* start = (unsigned long long*)h->scratch.p;
+    unsigned long long* seg_lo = start + n_in + 2;
+    unsigned long long* seg_hi = seg_lo + n_in + 2;
+    HIPC(hipMemcpyAsync(start, d_bucket_counts, (size_t)n_in * 8, hipMemcpyDeviceToDevice, h->stream));
+    hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, h->stream, start, (uint64_t)n_in, start + n_in);
+    hipLaunchKernelGGL(k_sharded_segments, dim3((n_in + 255) / 256), dim3(256), 0, h->stream, start, (const unsigned long long*)d_bucket_counts, (uint32_t)n_peers, seg_lo, seg_hi);
+    Dest dst{p.fmt, AUX_IDX6};
+    rc = dest_take(h, p, p.n_max, &dst); if (rc) return rc;
+    // the first level reads the received runs; the table pass visits the window's regions only, so records of foreign buckets
+    // are sorted and never applied
+    const LevelIn runs{d_recs, nullptr, seg_lo, seg_hi, n_in, (uint32_t)n_peers};
     return submit(h, sort_to_regions(h, &p, runs, dst), dst);
 }
 

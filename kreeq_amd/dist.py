@@ -1,18 +1,21 @@
 """Bucket-sharded multi-GPU counting: one process per GPU, torch.distributed (backend "nccl" is RCCL
 on ROCm) over xGMI.
 
-Two ownership rules, one per record format:
+Two ownership rules:
 
-* k <= 21 on tables of >= 2048 regions (the default k at any real size) -- HASH-PREFIX BUCKETS: rank r owns the buckets
-  [ceil(256 r / world), ceil(256 (r+1) / world)) of the top 8 bits of the table hash, and its table is the window of
-  those buckets (KQ_OPT_BUCKET_WINDOW).  The first split of the single-GPU count path (256 buckets) is then the owner
-  split as well: a rank scans its reads once, its bucket-sorted 5-byte records are already grouped by destination, one
-  all-to-all(v) routes them, and the receiver's split levels take the (bucket, peer) runs as their input segments -- the
-  N > 1 path runs the kernels of the single-GPU path and nothing more.  Validation: every rank evaluates the assembly
-  k-mers of its buckets; database files: the entries are routed to the rank that writes their map (export_db).
-* otherwise -- the reference's own bucket function: rank r owns maps [r*map_count/world, (r+1)*map_count/world) of
-  key % map_count (src/graph-builder.cpp:95, src/kreeq.cpp:146), records are grouped by owner in a split level of their
-  own (8-byte packed records up to k = 28, key + edge byte above); validation by map range (src/kreeq.cpp:150).
+* k <= 21 and k = 29..32 on tables of >= 2048 regions (the default k and the HiFi k at any real size) -- HASH-PREFIX
+  BUCKETS ("bucket mode"): rank r owns the buckets [ceil(256 r / world), ceil(256 (r+1) / world)) of the top 8 bits of the
+  table hash, and its table is the window of those buckets (KQ_OPT_BUCKET_WINDOW; KQ_OPT_SHARD_WINDOW for k = 29..32).
+  The first split of the single-GPU count path (256 buckets) is then the owner split as well: a rank scans its reads once,
+  its bucket-sorted records -- 5 bytes (u32 + u8) for k <= 21 (`sharded5`), one u64 hash remainder for k = 29..32
+  (`sharded8`) -- are already grouped by destination, one all-to-all(v) per array routes them, and the receiver's split
+  levels take the (bucket, peer) runs as their input segments: the N > 1 path runs the kernels of the single-GPU path and
+  nothing more.  Validation: every rank evaluates the assembly k-mers of its buckets; database files: the entries are routed
+  to the rank that writes their map (export_db).
+* otherwise (k = 22..28, and any k on a table below 2048 regions) -- the reference's own bucket function: rank r owns maps
+  [r*map_count/world, (r+1)*map_count/world) of key % map_count (src/graph-builder.cpp:95, src/kreeq.cpp:146), records are
+  grouped by owner in a split level of their own (8-byte packed records up to k = 28, key + edge byte -- 9 bytes in two
+  arrays -- above); validation by map range (src/kreeq.cpp:150).
 
 Per read batch every rank emits records from ITS reads, one all-to-all(v) per array routes them, every rank inserts what
 it received into its own table.  QV counters, summary numbers and the coverage histogram are all-reduced (sum).
@@ -109,14 +112,17 @@ class GpuEngine:
         self._send = {}
         # 5-byte records (u32 + u8, grouped by owner and hash-prefix bucket) when k <= 21 and the table has the 256-bucket
         # geometry (>= 2048 regions of 2048 slots); else 8-byte packed records (k <= 28) or key + edge byte
-        self.sharded5 = k <= 21 and self.db.info()["slots_total"] // 2048 >= 2048
+        regions = self.db.info()["slots_total"] // 2048
+        self.sharded5 = k <= 21 and regions >= 2048
+        # 8-byte hash-remainder records grouped the same way for k = 29..32; below 2048 regions the 9-byte path stays
+        self.sharded8 = 29 <= k <= 32 and regions >= 2048
 
     lazy_counts = True      # emit_partitioned(..., lazy=True) may return counts=None: the part sizes are meta.sum(dim=1) on the device
 
     def emit_partitioned(self, bases: torch.Tensor, n_parts: int, slot: int = 0, lazy: bool = False):
         """-> ([payload tensors grouped by owner part], per-part record counts).  `slot` selects one of
         two send buffers, so a chunk can be scanned while the previous one is still being exchanged.
-        lazy (5-byte records only): nothing is read back -- the payload tensors are the whole send buffers and counts is None;
+        lazy (bucket-sorted records only): nothing is read back -- the payload tensors are the whole send buffers and counts is None;
         the caller slices them once it knows the sizes (it exchanges the counts anyway: one host round trip instead of two)."""
         n = bases.numel()
         if self.sharded5:
@@ -131,6 +137,16 @@ class GpuEngine:
                 return [recs, aux], None, meta
             tot = int(counts.sum())
             return [recs[:tot], aux[:tot]], counts.astype(np.int64), meta
+        if self.sharded8:
+            buf = self._send.get(("s8", slot))
+            if buf is None or buf[0].numel() < n or buf[1].shape[0] != n_parts:
+                buf = (torch.empty(n, dtype=torch.int64, device=self.device), torch.empty((n_parts, 256), dtype=torch.int64, device=self.device))
+                self._send[("s8", slot)] = buf
+            recs, meta = buf
+            counts = self.db.emit_sharded8_dev(bases.data_ptr(), n, n_parts, recs.data_ptr(), recs.numel(), meta.data_ptr(), sync=not lazy)
+            if lazy:
+                return [recs], None, meta
+            return [recs[:int(counts.sum())]], counts.astype(np.int64), meta
         buf = self._send.get(slot)
         if buf is None or buf[0].numel() < n:
             buf = (torch.empty(n, dtype=torch.int64, device=self.device),
@@ -146,15 +162,17 @@ class GpuEngine:
         return [keys[:tot], edges[:tot]], counts.astype(np.int64)
 
     def set_window(self, bucket_lo, bucket_hi):
-        """this rank's table holds the hash-prefix buckets [bucket_lo, bucket_hi) only (KQ_OPT_BUCKET_WINDOW)"""
-        self.db.set_option("bucket_window", bucket_lo | (bucket_hi << 16))
+        """this rank's table holds the hash-prefix buckets [bucket_lo, bucket_hi) only (KQ_OPT_BUCKET_WINDOW; k = 29..32: KQ_OPT_SHARD_WINDOW)"""
+        self.db.set_option("shard_window" if self.sharded8 else "bucket_window", bucket_lo | (bucket_hi << 16))
 
     def count(self, bases: torch.Tensor):
         """fused K1+K2 (no record materialisation): the single-GPU path"""
         self.db.count_batch_dev(bases.data_ptr(), bases.numel())
 
     def insert(self, payload, meta=None):
-        if meta is not None:        # 5-byte records + [n_peers, 256] bucket counts
+        if meta is not None and len(payload) == 1:      # 8-byte hash-remainder records + [n_peers, 256] bucket counts
+            self.db.insert_sharded8_dev(payload[0].data_ptr(), payload[0].numel(), meta.shape[0], meta.data_ptr())
+        elif meta is not None:      # 5-byte records + [n_peers, 256] bucket counts
             self.db.insert_sharded_dev(payload[0].data_ptr(), payload[1].data_ptr(), payload[0].numel(), meta.shape[0], meta.data_ptr())
         elif len(payload) == 1:
             self.db.insert_packed_dev(payload[0].data_ptr(), payload[0].numel())
@@ -188,8 +206,9 @@ class GpuEngine:
 
 
 class ShardedCounter:
-    def __init__(self, engine, k, map_count=128, group=None, sharded_path=False):
-        """sharded_path=True runs emit -> (exchange) -> insert even on one rank (rehearsal of the N>1 code)"""
+    def __init__(self, engine, k, map_count=128, group=None, sharded_path=False, force_wide=False):
+        """sharded_path=True runs emit -> (exchange) -> insert even on one rank (rehearsal of the N>1 code);
+        force_wide=True (measurement) keeps k = 29..32 on the key + edge byte records of small tables whatever the table allows"""
         self.engine, self.k, self.map_count, self.group = engine, k, map_count, group
         self.sharded_path = sharded_path
         self.force_exchange = False
@@ -206,16 +225,25 @@ class ShardedCounter:
         # several ranks on ONE GPU; the product's backend is nccl = RCCL, which moves device memory directly)
         self.stage_host = (dist.is_initialized() and dist.get_backend(group) == "gloo"
                            and getattr(getattr(engine, "device", None), "type", "cpu") != "cpu")
-        # every rank must emit the record format every rank can insert: 5-byte records only if all tables allow them
-        if self.world > 1 and hasattr(engine, "sharded5"):
-            flag = torch.tensor([1 if engine.sharded5 else 0], dtype=torch.int64, device=getattr(engine, "device", torch.device("cpu")))
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=group)
-            engine.sharded5 = bool(flag.item())
+        # every rank must emit the record format every rank can insert: bucket-sorted records only if all tables allow them
+        self.force_wide = force_wide
+        if force_wide and hasattr(engine, "sharded8"):
+            engine.sharded8 = False
+        for attr in ("sharded5", "sharded8"):
+            if self.world > 1 and hasattr(engine, attr):
+                flag = torch.tensor([1 if getattr(engine, attr) else 0], dtype=torch.int64, device=getattr(engine, "device", torch.device("cpu")))
+                dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=group)
+                setattr(engine, attr, bool(flag.item()))
         # ownership by hash-prefix bucket range (module docstring): this rank's table becomes the window of its buckets
-        self.bucket_mode = bool(getattr(engine, "sharded5", False))
+        self.bucket_mode = self._bucket_records(engine)
         self.bucket_lo, self.bucket_hi = bucket_range(self.rank, self.world)
         if self.bucket_mode and self.world > 1:
             engine.set_window(self.bucket_lo, self.bucket_hi)
+
+    @staticmethod
+    def _bucket_records(engine):
+        """does the engine emit bucket-sorted records with per-(part, bucket) counts (5-byte or 8-byte hash-remainder)?"""
+        return bool(getattr(engine, "sharded5", False) or getattr(engine, "sharded8", False))
 
     def _stream_ctx(self):
         import contextlib
@@ -256,8 +284,8 @@ class ShardedCounter:
 
     @staticmethod
     def _emit(engine, bases, world, slot=0, lazy=False):
-        """-> (payload tensors, per-part counts, meta): meta = per-(part, bucket) counts of the 5-byte format, else None"""
-        if lazy and getattr(engine, "lazy_counts", False) and getattr(engine, "sharded5", False):
+        """-> (payload tensors, per-part counts, meta): meta = per-(part, bucket) counts of the bucket-sorted formats, else None"""
+        if lazy and getattr(engine, "lazy_counts", False) and ShardedCounter._bucket_records(engine):
             return engine.emit_partitioned(bases, world, slot=slot, lazy=True)
         res = engine.emit_partitioned(bases, world, slot=slot)
         return res if len(res) == 3 else (res[0], res[1], None)
@@ -375,7 +403,7 @@ class ShardedCounter:
         # 2^28 measured 31.4 ms per 1.3e9 k-mers, 2^27 37.5, 2^29 51.2); every rank must issue the same number of
         # collectives, so the chunk count is the maximum over the ranks (one small all-reduce per batch)
         n_total, pending = 0, None
-        rec_bytes = 4 if getattr(self.engine, "sharded5", False) else 8       # widest array of a record: u32 (+ a byte array), or u64
+        rec_bytes = 4 if getattr(self.engine, "sharded5", False) else 8       # widest array of a record: u32 (+ a byte array), or u64 (hash remainder, packed record or key)
         n_chunks = max(self.n_chunks, -(-bases.numel() // min(self.MAX_CHUNK_BASES, self.MAX_MESSAGE_BYTES // rec_bytes)))
         if self.world > 1:
             nc = torch.tensor([n_chunks], dtype=torch.int64, device=bases.device)
