@@ -362,6 +362,30 @@ int  kq_import(kq_handle* h, const kq_entry* entries, uint64_t n);
 int  kq_export(kq_handle* h, uint16_t map_lo, uint16_t map_hi, kq_entry* out, uint64_t cap,
                uint64_t* n_out);
 
+
+/* Replaces gfalibs dumpMap (and the host writer's insertion emulation): the complete bytes of <db>/.map.<m>.bin for every
+ * map m in [map_lo, map_hi), built on the device.  out + offsets[m - map_lo] .. out + offsets[m - map_lo + 1] is the file
+ * of map m (offsets: map_hi - map_lo + 1 values, host): the phmap dump of 256 submaps that sequential insertion in
+ * ascending unsigned key order gives, byte for byte what the host writer produces from kq_export's entries of the range.
+ * A high-copy k-mer (hc != 0) becomes the tombstone slot (cov 255, edges 0); those entries are returned in hc_out, sorted
+ * by key, for the single .map.hc.bin the host writes.  out == NULL: only offsets and *n_hc are filled (the size query: one
+ * pass over the table).  KQ_ERR_CAPACITY, with offsets and *n_hc set, when cap (bytes) or hc_cap (entries) is too small;
+ * KQ_ERR_INVALID for a bad range or null offsets / n_hc, before any device work, and for a range of 2^32 k-mers or more
+ * (take smaller ranges).  The image, the range's entries and the sort scratch must fit beside the table: choose ranges
+ * with the size query.  Flushes pending records; on a windowed handle the window's k-mers are exported.  Synchronises. */
+int  kq_export_map_images(kq_handle* h, uint16_t map_lo, uint16_t map_hi, void* out, uint64_t cap, uint64_t* offsets,
+                          kq_entry* hc_out, uint64_t hc_cap, uint64_t* n_hc);
+/* Replaces phmap_load of one <db>/.map.<m>.bin (gfalibs loadMapRange): `image` (host memory, page-locked or not) holds the
+ * whole file.  The 256 submap headers are walked and bound-checked on the host, the bytes go to the device as they are, one
+ * kernel checks every occupied slot (occupied count == size, key % map_count == map, cov > 0, no edge counter above cov)
+ * and a second one ADDS every slot with cov != 255 to the table (importing two databases == union).  Slots with cov == 255
+ * are tombstones: counted in *n_tombstones and skipped -- their counters are in .map.hc.bin, which the caller imports with
+ * kq_import and compares against the tombstone count.  A malformed image (submap count, version, truncated, trailing
+ * bytes, size mismatch, wrong map, invalid entry) is refused with KQ_ERR_INVALID and nothing is added; the header defects
+ * are found before any device work.  An empty map (6152 bytes) is KQ_OK without device work.  Synchronises. */
+int  kq_import_map_image(kq_handle* h, uint16_t map, const void* image, uint64_t n_bytes, uint64_t* n_entries,
+                         uint64_t* n_tombstones);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,8 @@ SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profi
            "kq_abi_version", "kq_device_available", "kq_device_memory", "kq_count_batch", "kq_count_batch_dev", "kq_host_alloc", "kq_host_free", "kq_count_batch_async", "kq_host_wait", "kq_pack_bases", "kq_count_packed_dev", "kq_count_packed_async",
            "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
-           "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_lookup_keys", "kq_branch_scan", "kq_merge", "kq_import", "kq_export"]
+           "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_lookup_keys", "kq_branch_scan", "kq_merge", "kq_import", "kq_export",
+           "kq_export_map_images", "kq_import_map_image"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
 
@@ -128,6 +129,8 @@ def load():
     L.kq_merge.argtypes = [vp, vp]
     L.kq_import.argtypes = [vp, vp, u64]
     L.kq_export.argtypes = [vp, u16, u16, vp, u64, C.POINTER(u64)]
+    L.kq_export_map_images.argtypes = [vp, u16, u16, vp, u64, vp, vp, u64, C.POINTER(u64)]
+    L.kq_import_map_image.argtypes = [vp, u16, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     _lib = L
     return L
 
@@ -380,3 +383,26 @@ class KreeqDB:
         if n.value:
             _check(load().kq_export(self._h, map_lo, map_hi, _p(out), n.value, C.byref(n)))
         return out
+
+    def export_map_images(self, map_lo=0, map_hi=None, sizes_only=False):
+        """-> (images, hc): images[i] = the bytes of <db>/.map.<map_lo + i>.bin (uint8 arrays), hc = the high-copy entries of
+        the range in key order.  sizes_only: -> (offsets u64[n_maps + 1], n_hc) from the size query alone"""
+        if map_hi is None:
+            map_hi = self.map_count
+        offsets = np.zeros(map_hi - map_lo + 1, dtype=np.uint64)
+        n_hc = C.c_uint64(0)
+        _check(load().kq_export_map_images(self._h, map_lo, map_hi, None, 0, _p(offsets), None, 0, C.byref(n_hc)))
+        if sizes_only:
+            return offsets, n_hc.value
+        buf = np.zeros(max(int(offsets[-1]), 1), dtype=np.uint8)
+        hc = np.zeros(max(n_hc.value, 1), dtype=ENTRY_DTYPE)
+        filled = np.zeros_like(offsets)
+        _check(load().kq_export_map_images(self._h, map_lo, map_hi, _p(buf), int(offsets[-1]), _p(filled), _p(hc), n_hc.value, C.byref(n_hc)))
+        return [buf[int(filled[i]):int(filled[i + 1])] for i in range(map_hi - map_lo)], hc[:n_hc.value]
+
+    def import_map_image(self, map_index, image):
+        """adds the k-mers of one <db>/.map.<m>.bin (bytes or a uint8 array); -> (entries added, tombstones skipped)"""
+        buf = np.frombuffer(image, dtype=np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else np.ascontiguousarray(image, dtype=np.uint8)
+        n, t = C.c_uint64(0), C.c_uint64(0)
+        _check(load().kq_import_map_image(self._h, map_index, _p(buf), len(buf), C.byref(n), C.byref(t)))
+        return n.value, t.value

@@ -25,6 +25,7 @@ using namespace kq;
 
 #include "kq_kernels.h"
 #include "kq_fastx.h"
+#include "kq_dbimage.h"
 
 // ================================================================================================
 // host side
@@ -2191,6 +2192,54 @@ int kq_import(kq_handle* h, const kq_entry* entries, uint64_t n) {
     return kq_sync(h);
 }
 
+// key order on the device: radix sort of (key, index) + gather into a fresh array (*d_sorted, the caller frees it).  false, and
+// nothing kept, when there is no memory for it (or n >= 2^32)
+static bool sort_entries_dev(kq_handle* h, const kq_entry* d_in, uint64_t n, kq_entry** d_sorted_out) {
+    kq_entry* d_sorted = nullptr; uint64_t *d_k1 = nullptr, *d_k2 = nullptr; uint32_t *d_i1 = nullptr, *d_i2 = nullptr; void* d_tmp = nullptr;
+    size_t tmp_bytes = 0;
+    bool on_device = n < (1ull << 32) &&
+        hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_k1, d_k2, d_i1, d_i2, (int64_t)n, 0, 2 * h->k, h->stream) == hipSuccess &&
+        hipMalloc((void**)&d_sorted, n * sizeof(kq_entry)) == hipSuccess && hipMalloc((void**)&d_k1, n * 8) == hipSuccess &&
+        hipMalloc((void**)&d_k2, n * 8) == hipSuccess && hipMalloc((void**)&d_i1, n * 4) == hipSuccess &&
+        hipMalloc((void**)&d_i2, n * 4) == hipSuccess && hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8) == hipSuccess;
+    if (on_device) {
+        hipLaunchKernelGGL(k_entry_keys, dim3(grid_for(h, n, 256)), dim3(256), 0, h->stream, d_in, n, d_k1, d_i1);
+        on_device = hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k1, d_k2, d_i1, d_i2, (int64_t)n, 0, 2 * h->k, h->stream) == hipSuccess;
+        if (on_device) {
+            hipLaunchKernelGGL(k_entry_gather, dim3(grid_for(h, n, 256)), dim3(256), 0, h->stream, d_in, d_i2, n, d_sorted);
+            on_device = hipStreamSynchronize(h->stream) == hipSuccess;
+        }
+    }
+    if (!on_device) (void)hipGetLastError();
+    for (void* q : {(void*)d_k1, (void*)d_k2, (void*)d_i1, (void*)d_i2, d_tmp, on_device ? nullptr : (void*)d_sorted}) if (q) (void)hipFree(q);
+    *d_sorted_out = on_device ? d_sorted : nullptr;
+    return on_device;
+}
+// device -> caller: through two pinned bounce buffers (a copy into pageable memory runs at a fraction of the PCIe
+// rate: 0.25 s for 850 MB); the DMA of chunk i+1 overlaps the host copy of chunk i
+static hipError_t copy_out_bounced(kq_handle* h, void* out, const void* src, size_t bytes) {
+    const size_t chunk = (size_t)16 << 20;
+    void* bounce[2] = {nullptr, nullptr};
+    hipError_t e;
+    if (bytes > 4 * chunk && hipHostMalloc(&bounce[0], chunk, hipHostMallocDefault) == hipSuccess && hipHostMalloc(&bounce[1], chunk, hipHostMallocDefault) == hipSuccess) {
+        const size_t n_chunks = (bytes + chunk - 1) / chunk;
+        auto len_of = [&](size_t c) { return std::min(chunk, bytes - c * chunk); };
+        e = hipMemcpyAsync(bounce[0], (const char*)src, len_of(0), hipMemcpyDeviceToHost, h->stream);
+        for (size_t c = 0; c < n_chunks && e == hipSuccess; ++c) {
+            e = hipStreamSynchronize(h->stream);
+            if (e == hipSuccess && c + 1 < n_chunks)
+                e = hipMemcpyAsync(bounce[(c + 1) & 1], (const char*)src + (c + 1) * chunk, len_of(c + 1), hipMemcpyDeviceToHost, h->stream);
+            memcpy((char*)out + c * chunk, bounce[c & 1], len_of(c));
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    } else {
+        (void)hipGetLastError();
+        e = hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost);
+    }
+    for (void* b : bounce) if (b) (void)hipHostFree(b);
+    return e;
+}
+
 int kq_export(kq_handle* h, uint16_t map_lo, uint16_t map_hi, kq_entry* out, uint64_t cap, uint64_t* n_out) {
     if (!h || !n_out) return fail(KQ_ERR_INVALID, "null argument");
     if (map_lo > map_hi || map_hi > h->map_count) return fail(KQ_ERR_INVALID, "map range [%u,%u) outside [0,%d]", map_lo, map_hi, h->map_count);
@@ -2215,54 +2264,155 @@ int kq_export(kq_handle* h, uint16_t map_lo, uint16_t map_hi, kq_entry* out, uin
     if (!rc && out) {
         if (n > cap) rc = fail(KQ_ERR_CAPACITY, "export buffer too small: need %llu, have %llu", n, (unsigned long long)cap);
         else if (n) {
-            // key order on the device (radix sort of (key, index) + gather) when there is memory for it, else on the host
-            const kq_entry* src = d_out;
-            kq_entry* d_sorted = nullptr; uint64_t *d_k1 = nullptr, *d_k2 = nullptr; uint32_t *d_i1 = nullptr, *d_i2 = nullptr; void* d_tmp = nullptr;
-            size_t tmp_bytes = 0;
-            bool on_device = n < (1ull << 32) &&
-                hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_k1, d_k2, d_i1, d_i2, (int64_t)n, 0, 2 * h->k, h->stream) == hipSuccess &&
-                hipMalloc((void**)&d_sorted, n * sizeof(kq_entry)) == hipSuccess && hipMalloc((void**)&d_k1, n * 8) == hipSuccess &&
-                hipMalloc((void**)&d_k2, n * 8) == hipSuccess && hipMalloc((void**)&d_i1, n * 4) == hipSuccess &&
-                hipMalloc((void**)&d_i2, n * 4) == hipSuccess && hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8) == hipSuccess;
-            if (on_device) {
-                hipLaunchKernelGGL(k_entry_keys, dim3(grid_for(h, n, 256)), dim3(256), 0, h->stream, d_out, n, d_k1, d_i1);
-                on_device = hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k1, d_k2, d_i1, d_i2, (int64_t)n, 0, 2 * h->k, h->stream) == hipSuccess;
-                if (on_device) {
-                    hipLaunchKernelGGL(k_entry_gather, dim3(grid_for(h, n, 256)), dim3(256), 0, h->stream, d_out, d_i2, n, d_sorted);
-                    on_device = hipStreamSynchronize(h->stream) == hipSuccess;
-                    src = d_sorted;
-                }
-            }
-            if (!on_device) { (void)hipGetLastError(); src = d_out; }
-            // device -> caller: through two pinned bounce buffers (a copy into pageable memory runs at a fraction of the PCIe
-            // rate: 0.25 s for 850 MB); the DMA of chunk i+1 overlaps the host copy of chunk i
-            const size_t bytes = (size_t)n * sizeof(kq_entry), chunk = (size_t)16 << 20;
-            void* bounce[2] = {nullptr, nullptr};
-            if (bytes > 4 * chunk && hipHostMalloc(&bounce[0], chunk, hipHostMallocDefault) == hipSuccess && hipHostMalloc(&bounce[1], chunk, hipHostMallocDefault) == hipSuccess) {
-                e = hipSuccess;
-                const size_t n_chunks = (bytes + chunk - 1) / chunk;
-                auto len_of = [&](size_t c) { return std::min(chunk, bytes - c * chunk); };
-                e = hipMemcpyAsync(bounce[0], (const char*)src, len_of(0), hipMemcpyDeviceToHost, h->stream);
-                for (size_t c = 0; c < n_chunks && e == hipSuccess; ++c) {
-                    e = hipStreamSynchronize(h->stream);
-                    if (e == hipSuccess && c + 1 < n_chunks)
-                        e = hipMemcpyAsync(bounce[(c + 1) & 1], (const char*)src + (c + 1) * chunk, len_of(c + 1), hipMemcpyDeviceToHost, h->stream);
-                    memcpy((char*)out + c * chunk, bounce[c & 1], len_of(c));
-                }
-                if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            } else {
-                (void)hipGetLastError();
-                e = hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost);
-            }
-            for (void* b : bounce) if (b) (void)hipHostFree(b);
+            // key order on the device when there is memory for it, else on the host
+            kq_entry* d_sorted = nullptr;
+            const bool on_device = sort_entries_dev(h, d_out, n, &d_sorted);
+            e = copy_out_bounced(h, out, on_device ? d_sorted : d_out, (size_t)n * sizeof(kq_entry));
             if (e != hipSuccess) rc = fail(KQ_ERR_HIP, "export copy failed: %s", hipGetErrorString(e));
             else if (!on_device) parallel_sort_entries(out, n);
-            for (void* q : {(void*)d_sorted, (void*)d_k1, (void*)d_k2, (void*)d_i1, (void*)d_i2, d_tmp}) if (q) (void)hipFree(q);
+            if (d_sorted) (void)hipFree(d_sorted);
         }
     }
     (void)hipFree(d_n);
     if (d_out) (void)hipFree(d_out);
     return rc;
+}
+
+// ---- database map files as device-built / device-parsed images (kq_dbimage.h) -----------------------------------------
+namespace {
+struct DevPtrs {                       // device allocations of one call, freed on every way out
+    std::vector<void*> v;
+    ~DevPtrs() { for (void* p : v) if (p) (void)hipFree(p); }
+    hipError_t alloc(void** p, size_t bytes) {
+        *p = nullptr;
+        hipError_t e = hipMalloc(p, bytes ? bytes : 8);
+        if (e == hipSuccess) v.push_back(*p); else (void)hipGetLastError();
+        return e;
+    }
+    void release(void* p) { for (void*& q : v) if (q == p) { (void)hipFree(q); q = nullptr; } }
+};
+}  // namespace
+
+int kq_export_map_images(kq_handle* h, uint16_t map_lo, uint16_t map_hi, void* out, uint64_t cap, uint64_t* offsets,
+                         kq_entry* hc_out, uint64_t hc_cap, uint64_t* n_hc) {
+    if (!offsets || !n_hc) return fail(KQ_ERR_INVALID, "null offsets / n_hc");
+    if (map_lo > map_hi) return fail(KQ_ERR_INVALID, "map range [%u,%u) is reversed", map_lo, map_hi);
+    if (!h) return fail(KQ_ERR_INVALID, "null handle");
+    if (map_hi > h->map_count) return fail(KQ_ERR_INVALID, "map range [%u,%u) outside [0,%d]", map_lo, map_hi, h->map_count);
+    const uint32_t n_maps = (uint32_t)(map_hi - map_lo), n_sub = n_maps * DBI_SUBMAPS;
+    offsets[0] = 0; *n_hc = 0;
+    if (!n_maps) return KQ_OK;
+    HIPC(hipSetDevice(h->device));
+    int rc = check_errors(h);          // flushes pending records
+    if (rc) return rc;
+    materialize(h);
+    DevPtrs mem;
+    // sizes: k-mers per (map, submap) + the high-copy count
+    unsigned long long* d_cnt = nullptr;
+    HIPC(mem.alloc((void**)&d_cnt, (size_t)(n_sub + 1) * 8));
+    HIPC(hipMemsetAsync(d_cnt, 0, (size_t)(n_sub + 1) * 8, h->stream));
+    hipLaunchKernelGGL(k_dbi_hist, dim3(grid_for(h, h->n_slots(), 256)), dim3(256), 0, h->stream, h->view(), (uint32_t)h->map_count,
+                       (uint32_t)map_lo, (uint32_t)map_hi, d_cnt);
+    HIPC(hipGetLastError());
+    std::vector<unsigned long long> cnt(n_sub + 1);
+    HIPC(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPC(hipStreamSynchronize(h->stream));
+    std::vector<ulonglong2> sub(n_sub + 1);                 // (byte offset of the submap's header, index of its first entry)
+    uint64_t bytes = 0, n = 0;
+    for (uint32_t s = 0; s < n_sub; ++s) {
+        if (s % DBI_SUBMAPS == 0) { offsets[s / DBI_SUBMAPS] = bytes; bytes += 8; }
+        sub[s] = make_ulonglong2(bytes, n);
+        bytes += dbi_submap_bytes(cnt[s]);
+        n += cnt[s];
+    }
+    offsets[n_maps] = bytes;
+    sub[n_sub] = make_ulonglong2(bytes, n);
+    *n_hc = cnt[n_sub];
+    if (!out) return KQ_OK;
+    if (cap < bytes) return fail(KQ_ERR_CAPACITY, "image buffer too small: need %llu bytes, have %llu", (unsigned long long)bytes, (unsigned long long)cap);
+    if (hc_cap < *n_hc || (*n_hc && !hc_out)) return fail(KQ_ERR_CAPACITY, "high-copy buffer too small: need %llu entries, have %llu", (unsigned long long)*n_hc, (unsigned long long)hc_cap);
+    if (n >= (1ull << 32)) return fail(KQ_ERR_INVALID, "%llu k-mers in maps [%u,%u): take the images in smaller map ranges (below 2^32 k-mers each)", (unsigned long long)n, map_lo, map_hi);
+    // logical entries of the range in key order: the filter, sort and gather of kq_export
+    kq_entry *d_ent = nullptr, *d_sorted = nullptr, *d_hc = nullptr;
+    uint64_t *d_r1 = nullptr, *d_r2 = nullptr;
+    unsigned long long *d_n = nullptr, *d_mat = nullptr;
+    if (n) {
+        if (mem.alloc((void**)&d_ent, (size_t)n * sizeof(kq_entry)) != hipSuccess) return fail(KQ_ERR_NOMEM, "no device memory for the %llu entries of maps [%u,%u)", (unsigned long long)n, map_lo, map_hi);
+        HIPC(hipMemsetAsync(d_cnt, 0, 16, h->stream));      // [0]: k_export's counter, [1]: high-copy cursor
+        d_n = d_cnt;
+        hipLaunchKernelGGL(k_export, dim3(grid_for(h, h->n_slots(), 1024)), dim3(256), 0, h->stream, h->view(), (uint32_t)h->map_count,
+                           (uint32_t)map_lo, (uint32_t)map_hi, d_ent, n, d_n);
+        HIPC(hipGetLastError());
+        if (!sort_entries_dev(h, d_ent, n, &d_sorted)) return fail(KQ_ERR_NOMEM, "no device memory to sort the %llu entries of maps [%u,%u)", (unsigned long long)n, map_lo, map_hi);
+        mem.v.push_back(d_sorted);
+        mem.release(d_ent);
+        // records + stable split by (map, submap), least significant digit first
+        const uint32_t G = (uint32_t)std::min<uint64_t>(1024, (n + 255) / 256);
+        const uint64_t chunk = ((n + G - 1) / G + 255) / 256 * 256;
+        if (mem.alloc((void**)&d_r1, (size_t)n * 8) != hipSuccess || mem.alloc((void**)&d_r2, (size_t)n * 8) != hipSuccess || mem.alloc((void**)&d_hc, (size_t)*n_hc * sizeof(kq_entry)) != hipSuccess ||
+            mem.alloc((void**)&d_mat, (size_t)256 * G * 8) != hipSuccess) return fail(KQ_ERR_NOMEM, "no device memory for the record split of maps [%u,%u)", map_lo, map_hi);
+        hipLaunchKernelGGL(k_dbi_records, dim3(grid_for(h, n, 256)), dim3(256), 0, h->stream, d_sorted, n, (uint32_t)h->map_count, (uint32_t)map_lo, d_r1, d_hc,
+                           (uint64_t)*n_hc, d_n + 1);
+        for (uint32_t shift = 32; (uint64_t)n_sub > (1ull << (shift - 32)); shift += 8) {
+            hipLaunchKernelGGL(k_dbi_split_hist, dim3(G), dim3(256), 0, h->stream, d_r1, n, chunk, shift, d_mat);
+            hipLaunchKernelGGL(k_dbi_split_scan, dim3(1), dim3(256), 0, h->stream, d_mat, G);
+            hipLaunchKernelGGL(k_dbi_split_scatter, dim3(G), dim3(256), 0, h->stream, d_r1, n, chunk, shift, d_mat, d_r2);
+            std::swap(d_r1, d_r2);
+        }
+        HIPC(hipGetLastError());
+    }
+    // the image
+    uint8_t* d_img = nullptr;
+    ulonglong2* d_sub = nullptr;
+    if (mem.alloc((void**)&d_img, (size_t)bytes) != hipSuccess || mem.alloc((void**)&d_sub, sub.size() * sizeof(ulonglong2)) != hipSuccess)
+        return fail(KQ_ERR_NOMEM, "no device memory for the %llu image bytes of maps [%u,%u)", (unsigned long long)bytes, map_lo, map_hi);
+    HIPC(hipMemsetAsync(d_img, 0, (size_t)bytes, h->stream));
+    HIPC(hipMemcpyAsync(d_sub, sub.data(), sub.size() * sizeof(ulonglong2), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_dbi_build, dim3(grid_for(h, n_sub, 4, 16)), dim3(256), 0, h->stream, d_sorted, d_r1, d_sub, n_sub, d_img);
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(h->stream));
+    hipError_t e = copy_out_bounced(h, out, d_img, (size_t)bytes);
+    if (e == hipSuccess && *n_hc) e = hipMemcpy(hc_out, d_hc, (size_t)*n_hc * sizeof(kq_entry), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(KQ_ERR_HIP, "image copy failed: %s", hipGetErrorString(e));
+    if (*n_hc) parallel_sort_entries(hc_out, *n_hc);
+    return KQ_OK;
+}
+
+int kq_import_map_image(kq_handle* h, uint16_t map, const void* image, uint64_t n_bytes, uint64_t* n_entries, uint64_t* n_tombstones) {
+    if (!image || !n_entries || !n_tombstones) return fail(KQ_ERR_INVALID, "null image / n_entries / n_tombstones");
+    *n_entries = 0; *n_tombstones = 0;
+    std::vector<DbiExtent> ext(DBI_SUBMAPS);
+    uint64_t total = 0;
+    if (const char* why = dbi_walk((const uint8_t*)image, n_bytes, ext.data(), &total)) return fail(KQ_ERR_INVALID, "%s (map %u)", why, map);
+    if (!h) return fail(KQ_ERR_INVALID, "null handle");
+    if (map >= h->map_count) return fail(KQ_ERR_INVALID, "map %u outside [0,%d)", map, h->map_count);
+    if (!total) return KQ_OK;                               // 6152 bytes: an empty map
+    HIPC(hipSetDevice(h->device));
+    DevPtrs mem;
+    uint8_t* d_img = nullptr; DbiExtent* d_ext = nullptr; DbiCheck* d_res = nullptr;
+    if (mem.alloc((void**)&d_img, (size_t)n_bytes) != hipSuccess || mem.alloc((void**)&d_ext, ext.size() * sizeof(DbiExtent)) != hipSuccess || mem.alloc((void**)&d_res, sizeof(DbiCheck)) != hipSuccess)
+        return fail(KQ_ERR_NOMEM, "no device memory for a map image of %llu bytes", (unsigned long long)n_bytes);
+    HIPC(hipMemcpyAsync(d_img, image, (size_t)n_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPC(hipMemcpyAsync(d_ext, ext.data(), ext.size() * sizeof(DbiExtent), hipMemcpyHostToDevice, h->stream));
+    HIPC(hipMemsetAsync(d_res, 0, sizeof(DbiCheck), h->stream));
+    hipLaunchKernelGGL(k_dbi_check, dim3(DBI_SUBMAPS), dim3(256), 0, h->stream, d_img, d_ext, (uint32_t)h->k, (uint32_t)h->map_count, (uint32_t)map, d_res);
+    HIPC(hipGetLastError());
+    DbiCheck res;
+    HIPC(hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, h->stream));
+    HIPC(hipStreamSynchronize(h->stream));
+    if (res.bad_size) return fail(KQ_ERR_INVALID, "inconsistent submap size in the image of map %u", map);
+    if (res.bad_map) return fail(KQ_ERR_INVALID, "%llu k-mers of the image do not belong to map %u", res.bad_map, map);
+    if (res.bad_entry) return fail(KQ_ERR_INVALID, "%llu slots of the image of map %u are no valid k-mer records (cov 0, or an edge counter above cov)", res.bad_entry, map);
+    int rc = reserve(h, total, res.instances);
+    if (rc) return rc;
+    materialize(h);
+    h->table_empty = false;
+    hipLaunchKernelGGL(k_dbi_add, dim3(DBI_SUBMAPS), dim3(256), 0, h->stream, h->view(), d_img, d_ext);
+    HIPC(hipGetLastError());
+    rc = kq_sync(h);
+    if (rc) return rc;
+    *n_entries = res.n_entries; *n_tombstones = res.n_tombstones;
+    return KQ_OK;
 }
 
 }  // extern "C"

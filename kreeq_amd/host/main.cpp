@@ -60,6 +60,65 @@ void verbose(const std::string& s) { if (verbose_flag) fprintf(stderr, "[%8.3f s
 }
 void kq_or_die(int rc) { if (rc != KQ_OK) die(std::string("Error: ") + kq_last_error()); }
 
+// KQ_DB_DEVICE=1: the .map.<m>.bin files are built and parsed on the GPU (kq_export_map_images / kq_import_map_image) instead
+// of entry by entry on the host; every file and stdout are byte-identical in both modes.  KQ_DB_TRACE=1 prints the wall
+// clock of the database steps of either mode to stderr.
+bool db_device() { static const bool on = [] { const char* e = getenv("KQ_DB_DEVICE"); return e && atoi(e) != 0; }(); return on; }
+struct DbTrace {
+    const char* what; double t0 = now_s(); uint64_t pcie = 0;
+    explicit DbTrace(const char* w) : what(w) {}
+    ~DbTrace() {
+        static const bool on = [] { const char* e = getenv("KQ_DB_TRACE"); return e && atoi(e) != 0; }();
+        if (on) fprintf(stderr, "[db] %s: %.3f s, %llu bytes over PCIe (%s)\n", what, now_s() - t0, (unsigned long long)pcie, db_device() ? "device" : "host");
+    }
+};
+// the files of maps [lo, hi) from the table of h, in sub-ranges whose image, entries and sort scratch fit the free HBM;
+// the high-copy entries are appended to hc_all for write_db_finish
+uint64_t write_db_maps_device(kq_handle* h, int device, const std::string& db, int lo, int hi, std::vector<kq_entry>& hc_all) {
+    ::mkdir(db.c_str(), 0777);
+    std::vector<uint64_t> off((size_t)(hi - lo) + 1);
+    uint64_t n_hc = 0, bytes_out = 0;
+    kq_or_die(kq_export_map_images(h, (uint16_t)lo, (uint16_t)hi, nullptr, 0, off.data(), nullptr, 0, &n_hc));
+    uint64_t free_b = 0, total_b = 0;
+    if (kq_device_memory(device, &free_b, &total_b) != KQ_OK) free_b = 8ull << 30;
+    // a slot is 24 bytes at a load of at most 7/8: an image of B bytes holds at most B / 27 k-mers, each of which takes
+    // 48 B as an entry twice (unsorted, sorted), 24 B of sort keys and 16 B of split records beside the image: < 6 B in all
+    const uint64_t budget = std::max<uint64_t>(free_b / 2 / 6, 1);
+    std::vector<uint8_t> img;
+    std::vector<kq_entry> hc;
+    for (int a = lo; a < hi;) {
+        int b = a + 1;
+        while (b < hi && off[(size_t)(b + 1 - lo)] - off[(size_t)(a - lo)] <= budget) ++b;
+        std::vector<uint64_t> o((size_t)(b - a) + 1);
+        kq_or_die(kq_export_map_images(h, (uint16_t)a, (uint16_t)b, nullptr, 0, o.data(), nullptr, 0, &n_hc));
+        img.resize((size_t)o.back());
+        hc.resize((size_t)n_hc);
+        kq_or_die(kq_export_map_images(h, (uint16_t)a, (uint16_t)b, img.data(), img.size(), o.data(), hc.data(), hc.size(), &n_hc));
+        for (int m = a; m < b; ++m) {
+            const std::string path = db + "/.map." + std::to_string(m) + ".bin";
+            FILE* f = fopen(path.c_str(), "wb");
+            const size_t len = (size_t)(o[(size_t)(m + 1 - a)] - o[(size_t)(m - a)]);
+            if (!f || fwrite(img.data() + o[(size_t)(m - a)], 1, len, f) != len || fclose(f) != 0) die("Error: cannot write " + path);
+        }
+        hc_all.insert(hc_all.end(), hc.begin(), hc.end());
+        bytes_out += img.size() + hc.size() * sizeof(kq_entry);
+        a = b;
+    }
+    return bytes_out;
+}
+// maps [lo, hi) of the table of h -> their files, on the host or on the device; returns the bytes that crossed PCIe
+void export_db_maps(kq_handle* h, int device, const std::string& db, int map_count, int lo, int hi, std::vector<kq_entry>& hc_all) {
+    DbTrace tr("export + write maps");
+    if (db_device()) { tr.pcie = write_db_maps_device(h, device, db, lo, hi, hc_all); return; }
+    uint64_t n = 0;
+    kq_or_die(kq_export(h, (uint16_t)lo, (uint16_t)hi, nullptr, 0, &n));
+    std::vector<kq_entry> entries((size_t)n);
+    if (n) kq_or_die(kq_export(h, (uint16_t)lo, (uint16_t)hi, entries.data(), n, &n));
+    verbose("Table exported (" + std::to_string(n) + " k-mers)");
+    tr.pcie = n * sizeof(kq_entry);
+    write_db_maps(db, map_count, lo, hi, entries, hc_all);
+}
+
 bool is_number(const char* s) { if (!*s) return false; for (; *s; ++s) if (*s < '0' || *s > '9') return false; return true; }
 bool is_int(const char* s) { if (*s == '-' || *s == '+') ++s; return is_number(s); }
 void if_file_exists(const char* p) {
@@ -168,12 +227,9 @@ struct Engine {
     }
 
     void write_kreeq_db(const std::string& dir) {
-        uint64_t n = 0;
-        kq_or_die(kq_export(h, 0, (uint16_t)map_count, nullptr, 0, &n));
-        std::vector<kq_entry> entries((size_t)n);
-        if (n) kq_or_die(kq_export(h, 0, (uint16_t)map_count, entries.data(), n, &n));
-        verbose("Table exported (" + std::to_string(n) + " k-mers)");
-        write_db(dir, k, map_count, entries);
+        std::vector<kq_entry> hc;
+        export_db_maps(h, ui.device, dir, map_count, 0, map_count, hc);
+        write_db_finish(dir, k, map_count, hc);
     }
 
     // .kwig (src/kreeq-output.cpp:243-303) and .bkwig (:305-399)
@@ -511,8 +567,36 @@ struct DbSource {
         return n;
     }
     static size_t chunk_entries() { const char* e = getenv("KQ_DB_CHUNK_ENTRIES"); return e ? (size_t)std::max(1ll, atoll(e)) : ((size_t)1 << 25); }   // 1.6 GB of host memory
+    // KQ_DB_DEVICE: every map file goes to the GPU as it lies on disk, through one reused page-locked buffer
+    uint64_t import_into_device(kq_handle* h, int lo, int hi, uint64_t& pcie) const {
+        uint64_t total = 0, n_tomb = 0, cap = 0;
+        for (int m = lo; m < hi; ++m) cap = std::max(cap, file_size(dir + "/.map." + std::to_string(m) + ".bin"));
+        uint8_t* buf = (uint8_t*)kq_host_alloc(std::max<uint64_t>(cap, 1));
+        if (!buf) die("Error: cannot allocate a page-locked buffer for the map files");
+        for (int m = lo; m < hi; ++m) {
+            const std::string path = dir + "/.map." + std::to_string(m) + ".bin";
+            FILE* f = fopen(path.c_str(), "rb");
+            if (!f) die("Error: cannot open " + path);
+            const size_t len = fread(buf, 1, (size_t)cap, f);
+            const bool whole = len < cap || fgetc(f) == EOF;            // the file did not grow behind the size taken above
+            fclose(f);
+            if (!whole) die("Error: " + path + " changed while it was read");
+            uint64_t n = 0, t = 0;
+            kq_or_die(kq_import_map_image(h, (uint16_t)m, buf, len, &n, &t));
+            total += n; n_tomb += t; pcie += len;
+        }
+        kq_host_free(buf);
+        std::vector<kq_entry> v;                                    // the range's high-copy entries, as read_db_maps appends them
+        for (auto& e : hc) { const int m = (int)(e.key % (uint64_t)idx.map_count); if (m >= lo && m < hi) v.push_back(e); }
+        if (n_tomb > v.size()) die("Error: int32 map missing 255 value from int8 map");   // src/kreeq.cpp:162
+        kq_or_die(kq_import(h, v.data(), v.size()));
+        pcie += v.size() * sizeof(kq_entry);
+        return total + v.size();
+    }
     // ADDS the maps [lo, hi) to the table of h
     uint64_t import_into(kq_handle* h, int lo, int hi) const {
+        DbTrace tr("read + import maps");
+        if (db_device()) return import_into_device(h, lo, hi, tr.pcie);
         std::vector<kq_entry> v;
         uint64_t total = 0;
         const size_t chunk = chunk_entries();
@@ -524,6 +608,7 @@ struct DbSource {
             read_db_maps(dir, idx, a, b, hc, v);
             kq_or_die(kq_import(h, v.data(), v.size()));
             total += v.size();
+            tr.pcie += v.size() * sizeof(kq_entry);
             a = b;
         }
         return total;
@@ -640,13 +725,7 @@ int run_passes(Engine& e, const DbSource* db) {
             if (n) kq_or_die(kq_histogram(e.h, cov.data(), cnt.data(), n, &n));
             for (uint64_t i = 0; i < n; ++i) hist[cov[i]] += cnt[i];
         }
-        if (!range_db.empty()) {
-            uint64_t n = 0;
-            kq_or_die(kq_export(e.h, (uint16_t)lo, (uint16_t)hi, nullptr, 0, &n));
-            std::vector<kq_entry> entries((size_t)n);
-            if (n) kq_or_die(kq_export(e.h, (uint16_t)lo, (uint16_t)hi, entries.data(), n, &n));
-            write_db_maps(range_db, e.map_count, lo, hi, entries, hc_all);
-        }
+        if (!range_db.empty()) export_db_maps(e.h, ui.device, range_db, e.map_count, lo, hi, hc_all);
     }
     if (!range_db.empty()) write_db_finish(range_db, e.k, e.map_count, hc_all);
     if (want_stats) {
@@ -785,13 +864,7 @@ int run(UserInput& ui) {
                     if (n) kq_or_die(kq_histogram(e.h, cov.data(), cnt.data(), n, &n));
                     for (uint64_t i = 0; i < n; ++i) hist[cov[i]] += cnt[i];
                 }
-                if (ext == "kreeq") {
-                    uint64_t n = 0;
-                    kq_or_die(kq_export(e.h, (uint16_t)r.first, (uint16_t)r.second, nullptr, 0, &n));
-                    std::vector<kq_entry> entries((size_t)n);
-                    if (n) kq_or_die(kq_export(e.h, (uint16_t)r.first, (uint16_t)r.second, entries.data(), n, &n));
-                    write_db_maps(ui.outFile, map_count, r.first, r.second, entries, hc_all);
-                }
+                if (ext == "kreeq") export_db_maps(e.h, ui.device, ui.outFile, map_count, r.first, r.second, hc_all);
             }
             if (want_stats) {
                 const uint64_t space = k < 32 ? (1ull << (2 * k)) : 0ull;
