@@ -156,7 +156,10 @@ void* kq_get_stream(kq_handle* h);
  *                          (tools/bench_extra/alt_kernels.sh, bench.py --alt-kernels): 1 = P1 scatter of narrow and hash-remainder records with k_p1_scatter
  *                          (round 2's) instead of k_p1_scatter_s, 2 = split levels that write narrow records with k_lv_scatter_s (the
  *                          streamed formulation, which lost there) instead of k_lv_scatter, 4 = the level that writes tight records
- *                          with k_lv_scatter (round 2's) instead of k_lv_scatter_s.  Default 0. */
+ *                          with k_lv_scatter (round 2's) instead of k_lv_scatter_s, 16 = the table pass of 4- and 5-byte records with
+ *                          k_count_regions_q4 (every wave reads its region's offsets from the sets' own offset arrays, through the
+ *                          descriptors in memory, and the region's totals go to the table state with two atomics per region) instead of
+ *                          k_p3_region_offsets + k_count_regions_q4r + k_fold_totals.  (8 is not assigned.)  Default 0. */
 enum { KQ_OPT_TRUST_CAPACITY = 1, KQ_OPT_COUNT_PATH = 2, KQ_OPT_SLICE_KMERS = 3, KQ_OPT_COUNT_MAP_RANGE = 4, KQ_OPT_PROFILE = 5,
        KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13, KQ_OPT_SHARD_WINDOW = 14,
        KQ_OPT_TEST_FAIL_PLAN = 100 /* failure-path tests only: the next partition plan of a count fails with KQ_ERR_NOMEM */ };

@@ -704,12 +704,23 @@ template <class T> __device__ __forceinline__ T ld_global(const T* p) { return *
 // A wave's view of the pending sets of one region: lane q < n_sets holds set q's share (first record, record count,
 // first ticket); tickets = groups of GRP records, set after set.  Built by every wave for itself (two loads + a wave
 // scan, no LDS, no barrier); a ticket is located with one ballot.
-template <uint32_t GRP>
+// LO = uint32_t: built from the region-major offset matrix of the pass (k_p3_region_offsets: a set holds < 2^32 records).
+template <uint32_t GRP, class LO = uint64_t>
 struct SetTickets {
-    uint64_t lo; uint32_t cnt, first, n_grp;
+    LO lo; uint32_t cnt, first, n_grp;
     __device__ __forceinline__ void build(const P3Set* __restrict__ sets, uint32_t n_sets, uint64_t r, uint32_t lane) {
         lo = 0; cnt = 0;
-        if (lane < n_sets) { const unsigned long long* b = ld_global(&sets[lane].base); lo = ld_global(b + r); cnt = (uint32_t)(ld_global(b + r + 1) - lo); }   // a region holds < 2^32 records of one set
+        if (lane < n_sets) { const unsigned long long* b = ld_global(&sets[lane].base); lo = (LO)ld_global(b + r); cnt = (uint32_t)(ld_global(b + r + 1) - lo); }   // a region holds < 2^32 records of one set
+        scan(lane);
+    }
+    // the same from rows r and r + 1 of roff[][pitch] (columns >= n_sets hold 0 in every row: empty sets): two independent
+    // loads, each one coalesced row piece per wave, and no pointer is fetched from memory on the way
+    __device__ __forceinline__ void build(const uint32_t* __restrict__ roff, uint32_t pitch, uint64_t r, uint32_t lane) {
+        lo = 0; cnt = 0;
+        if (lane < pitch) { const uint32_t* p = roff + r * pitch + lane; const uint32_t a = ld_global(p), b = ld_global(p + pitch); lo = a; cnt = b - a; }
+        scan(lane);
+    }
+    __device__ __forceinline__ void scan(uint32_t lane) {
         const uint32_t mine = (cnt + GRP - 1) / GRP;
         uint32_t incl = mine;
 #pragma unroll
@@ -724,7 +735,8 @@ struct SetTickets {
         q = (g < n_grp && m) ? 63u - (uint32_t)__clzll((unsigned long long)m) : (uint32_t)__ffsll((unsigned long long)nonempty) - 1u;
         const uint32_t f = __builtin_amdgcn_readlane(first, q);
         q_cnt = __builtin_amdgcn_readlane(cnt, q);
-        q_lo = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(lo >> 32), q) << 32) | __builtin_amdgcn_readlane((uint32_t)lo, q);
+        if constexpr (sizeof(LO) == 8) q_lo = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)((uint64_t)lo >> 32), q) << 32) | __builtin_amdgcn_readlane((uint32_t)lo, q);
+        else q_lo = __builtin_amdgcn_readlane((uint32_t)lo, q);
         off = (g < n_grp ? g - f : 0u) * GRP;
     }
 };
@@ -735,11 +747,11 @@ struct SetTickets {
 // since that launch initialises every region, also the ones without records.  A region that receives far more records than
 // it has slots goes to hot_list: folding costs a ballot + shuffle per iteration, so only such regions (skew, or very deep
 // coverage) take that path, in the second launch.  HOT = that launch: it walks every listed region.
-template <int THREADS, bool HOT, uint32_t GRP>
-__device__ __forceinline__ bool region_gate(SetTickets<GRP>& tk, const TableView& t, const P3Set* __restrict__ sets, uint32_t n_sets, uint64_t r,
-                                            int table_is_empty, unsigned long long* __restrict__ hot_list /*[0] = count, then region ids*/) {
+// (region_gate_built: the same behind a ticket build of the caller's)
+template <int THREADS, bool HOT, class TK>
+__device__ __forceinline__ bool region_gate_built(const TK& tk, const TableView& t, uint64_t r,
+                                                  int table_is_empty, unsigned long long* __restrict__ hot_list /*[0] = count, then region ids*/) {
     const int tid = threadIdx.x;
-    tk.build(sets, n_sets, r, (uint32_t)tid & 63u);
     uint64_t n_recs = tk.cnt;                                           // block-uniform after the reduction
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n_recs += __shfl_xor(n_recs, o, 64);
@@ -755,6 +767,12 @@ __device__ __forceinline__ bool region_gate(SetTickets<GRP>& tk, const TableView
         return false;
     }
     return true;
+}
+template <int THREADS, bool HOT, uint32_t GRP>
+__device__ __forceinline__ bool region_gate(SetTickets<GRP>& tk, const TableView& t, const P3Set* __restrict__ sets, uint32_t n_sets, uint64_t r,
+                                            int table_is_empty, unsigned long long* __restrict__ hot_list) {
+    tk.build(sets, n_sets, r, threadIdx.x & 63u);
+    return region_gate_built<THREADS, HOT>(tk, t, r, table_is_empty, hot_list);
 }
 // High-copy tier of one region, aggregated in LDS (each kernel declares the two arrays): a repeat k-mer with millions of
 // instances would otherwise serialise millions of global atomics on one side-table entry.
@@ -810,6 +828,26 @@ __device__ __forceinline__ void region_totals_store(const TableView& t, const C&
         if (s_new) atomicAdd(&t.st->slots_used, (unsigned long long)s_new);
         if (s_kmers) atomicAdd(&t.st->kmers_added, (unsigned long long)s_kmers);
     }
+}
+
+// The same with the sums spread over TOT_LINES 64-byte lines (line = region mod TOT_LINES; k_fold_totals adds them to the table
+// state behind the pass): two atomics per region visit on ONE address each are a queue every workgroup of the pass stands in.
+constexpr uint32_t TOT_LINES = 4096;
+template <class C>
+__device__ __forceinline__ void region_totals_store(const TableView& t, unsigned long long* __restrict__ part, uint64_t r, const C& s_new, const C& s_kmers) {
+    if (!part) { region_totals_store(t, s_new, s_kmers); return; }
+    if (threadIdx.x == 0) {
+        unsigned long long* p = part + (r & (TOT_LINES - 1)) * 8;
+        if (s_new) atomicAdd(p, (unsigned long long)s_new);
+        if (s_kmers) atomicAdd(p + 1, (unsigned long long)s_kmers);
+    }
+}
+__global__ __launch_bounds__(256) void k_fold_totals(unsigned long long* __restrict__ part, DevState* __restrict__ st) {
+    unsigned long long a = 0, b = 0;
+    for (uint32_t i = threadIdx.x; i < TOT_LINES; i += 256) { a += part[i * 8]; b += part[i * 8 + 1]; part[i * 8] = 0; part[i * 8 + 1] = 0; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); b += __shfl_down(b, o, 64); }
+    if ((threadIdx.x & 63) == 0) { if (a) atomicAdd(&st->slots_used, a); if (b) atomicAdd(&st->kmers_added, b); }
 }
 
 #ifndef KQ_P3_THREADS
@@ -1071,9 +1109,34 @@ constexpr uint32_t Q4_EMPTY = 0xFFFFFFFFu, Q4_TOMB = 1u << 31;
 #define KQ_Q4_OCC 4
 #endif
 constexpr int Q4_THREADS = KQ_Q4_THREADS;
-template <int KC, bool TIGHT>
-__global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(TableView t, const P3Set* __restrict__ sets, uint32_t n_sets, int table_is_empty,
-                                                                     unsigned long long* __restrict__ hot_list, uint32_t rps) {
+// Where the pass finds its sets and where a region's totals go.  Q4SetsPtr (the previous pass, KQ_OPT_KERNEL_SET bit 16): the
+// descriptor array in memory, as the other region kernels read it -- lane q chases sets[q].base and then base[r], base[r + 1] in
+// the set's own offset array, every ticket fetches sets[q].recs / .aux again -- and two atomics per region on the table state.
+// Q4SetsRow (the shipped one): the region-major matrix k_p3_region_offsets makes once per pass, the record pointers of all sets by
+// value in the argument block (1 KiB of the 4 KiB a kernel may take): row pair -> records; the totals spread over TOT_LINES lines.
+// Measured at 3 Gbp: the offsets' two round trips less are 1 % of a pass, the atomics were a third of it.
+struct Q4SetsPtr {
+    using Lo = uint64_t;
+    const P3Set* __restrict__ sets; uint32_t n_sets;
+    template <class TK> __device__ __forceinline__ void build(TK& tk, uint64_t r, uint32_t lane) const { tk.build(sets, n_sets, r, lane); }
+    __device__ __forceinline__ const uint32_t* recs(uint32_t q) const { return reinterpret_cast<const uint32_t*>(sets[q].recs); }
+    __device__ __forceinline__ const uint8_t* aux(uint32_t q) const { return sets[q].aux; }
+    __device__ __forceinline__ unsigned long long* totals() const { return nullptr; }
+};
+struct Q4SetsRow {
+    using Lo = uint32_t;
+    const uint32_t* __restrict__ roff; uint32_t pitch;
+    unsigned long long* tot;             // [TOT_LINES][8]: the pass's sums of slots claimed / instances applied, or null
+    struct { const uint32_t* recs; const uint8_t* aux; } d[P3_MAX_SETS];
+    template <class TK> __device__ __forceinline__ void build(TK& tk, uint64_t r, uint32_t lane) const { tk.build(roff, pitch, r, lane); }
+    // q is wave-uniform (SetTickets::locate); said aloud, because a wave's first ticket is its wave number, which the compiler
+    // takes for a per-lane value -- and then reads the argument block with a vector load
+    __device__ __forceinline__ const uint32_t* recs(uint32_t q) const { return d[__builtin_amdgcn_readfirstlane(q)].recs; }
+    __device__ __forceinline__ const uint8_t* aux(uint32_t q) const { return d[__builtin_amdgcn_readfirstlane(q)].aux; }
+    __device__ __forceinline__ unsigned long long* totals() const { return tot; }
+};
+template <int KC, bool TIGHT, class SRC>
+__device__ __forceinline__ void count_regions_q4(const TableView& t, const SRC& src, int table_is_empty, unsigned long long* __restrict__ hot_list, uint32_t rps) {
     constexpr int PF = TIGHT ? KQ_Q4_PF_TIGHT : KQ_P3_PF;
     constexpr uint32_t GRP = 64u * PF;
     constexpr uint32_t QCAP = KQ_Q4_QCAP, NONE = 0xFFFFFFFFu;
@@ -1092,8 +1155,9 @@ __global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(Tabl
     const uint32_t k = KC ? KC : t.k;
     const uint32_t off_shift = 42 - 2 * k;                              // k <= 21
     for (uint64_t r = t.reg_lo + blockIdx.x; r < t.reg_hi; r += gridDim.x) {
-        SetTickets<GRP> tk;
-        if (!region_gate<Q4_THREADS, false>(tk, t, sets, n_sets, r, table_is_empty, hot_list)) continue;
+        SetTickets<GRP, typename SRC::Lo> tk;
+        src.build(tk, r, lane);
+        if (!region_gate_built<Q4_THREADS, false>(tk, t, r, table_is_empty, hot_list)) continue;
         ulonglong2* gimg = reinterpret_cast<ulonglong2*>(t.slots + (r << REGION_SHIFT));
         // the first records of this wave are requested NOW: their latency (an HBM round trip behind the ticket build's two)
         // runs under the image set-up and the barrier instead of behind them (round 3: a region visit is mostly such
@@ -1103,8 +1167,8 @@ __global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(Tabl
         auto fetch = [&](uint32_t g, uint32_t (&rec)[PF], uint32_t (&aux)[PF], uint32_t& n) {
             uint32_t q, off, cnt; uint64_t lo_q;
             tk.locate(g, q, off, cnt, lo_q);
-            const uint32_t* rp = reinterpret_cast<const uint32_t*>(sets[q].recs);
-            const uint8_t* ap = sets[q].aux;
+            const uint32_t* rp = src.recs(q);
+            const uint8_t* ap = src.aux(q);
             n = min(cnt - off, GRP);
 #pragma unroll
             for (int qq = 0; qq < PF; ++qq) {
@@ -1265,7 +1329,39 @@ __global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(Tabl
             }
             gimg[i] = o;
         }
-        region_totals_store(t, s_new, s_kmers);
+        region_totals_store(t, src.totals(), r, s_new, s_kmers);
+        __syncthreads();
+    }
+}
+template <int KC, bool TIGHT>
+__global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4(TableView t, const P3Set* __restrict__ sets, uint32_t n_sets, int table_is_empty,
+                                                                     unsigned long long* __restrict__ hot_list, uint32_t rps) {
+    count_regions_q4<KC, TIGHT>(t, Q4SetsPtr{sets, n_sets}, table_is_empty, hot_list, rps);
+}
+template <int KC, bool TIGHT>
+__global__ __launch_bounds__(Q4_THREADS, KQ_Q4_OCC) void k_count_regions_q4r(TableView t, Q4SetsRow src, int table_is_empty,
+                                                                      unsigned long long* __restrict__ hot_list, uint32_t rps) {
+    count_regions_q4<KC, TIGHT>(t, src, table_is_empty, hot_list, rps);
+}
+
+// roff[r][s] = (uint32_t)sets[s].base[row0 + r] for r in [0, n_rows), s < n_sets, and 0 in the columns [n_sets, pitch): the pending sets'
+// offset arrays, transposed once per table pass so that a region visit reads its share of every set as one row pair.  A
+// workgroup takes 64 rows: wave w reads 64 consecutive offsets of the sets w, w + 4, ... (512 contiguous bytes each) into an
+// LDS tile, and the tile's rows -- contiguous in roff, the pitch being the row length -- go out in full lines.
+constexpr int ROFF_THREADS = 256, ROFF_ROWS = 64;
+__global__ __launch_bounds__(ROFF_THREADS) void k_p3_region_offsets(uint32_t* __restrict__ roff, const P3Set* __restrict__ sets, uint32_t n_sets, uint32_t pitch, uint64_t row0, uint64_t n_rows) {
+    __shared__ uint32_t s_t[ROFF_ROWS][P3_MAX_SETS + 1];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * ROFF_ROWS; r0 < n_rows; r0 += (uint64_t)gridDim.x * ROFF_ROWS) {
+        const uint32_t rows = (uint32_t)min((uint64_t)ROFF_ROWS, n_rows - r0);
+        for (uint32_t s = wave; s < pitch; s += ROFF_THREADS / 64) {
+            uint32_t v = 0;
+            if (s < n_sets && lane < rows) v = (uint32_t)ld_global(ld_global(&sets[s].base) + row0 + r0 + lane);
+            s_t[lane][s] = v;
+        }
+        __syncthreads();
+        uint32_t* out = roff + r0 * pitch;
+        for (uint32_t i = threadIdx.x; i < rows * pitch; i += ROFF_THREADS) out[i] = s_t[i / pitch][i % pitch];
         __syncthreads();
     }
 }

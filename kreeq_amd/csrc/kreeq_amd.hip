@@ -20,6 +20,7 @@
 #include "../../include/kreeq_amd.h"
 #include "kq_device.h"
 #include "kq_partition.h"
+#include "kq_roff_host.h"
 
 using namespace kq;
 
@@ -180,6 +181,9 @@ struct kq_handle {
     void* arena = nullptr; size_t arena_bytes = 0, arena_used = 0;
     Scrambled arena_scr;                 // owns `arena` when it is a scrambled buffer (KQ_SCRAMBLE_ARENA)
     P3Set* d_sets = nullptr;             // device array [P3_MAX_SETS]
+    P3Set pend_sets[P3_MAX_SETS] = {};   // the same on the host: the record pointers travel in k_count_regions_q4r's argument block
+    unsigned long long* tot = nullptr;   // [TOT_LINES][8] partial sums of a table pass (k_fold_totals), zero between passes
+    DevBuf roff;                         // region-major offset matrix of a table pass (k_p3_region_offsets): (allocated regions + 1) x P3_MAX_SETS u32
     int n_pend = 0, pend_fmt = -1, pend_aux_fmt = 0;
     uint64_t pend_records = 0;           // upper bound of the records in the pending sets
     int64_t pend_budget = -1;            // KQ_OPT_PENDING_BYTES: -1 auto, 0 = apply every slice at once
@@ -583,6 +587,8 @@ void kq_destroy(kq_handle* h) {
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     arena_release(h);
     if (h->d_sets) (void)hipFree(h->d_sets);
+    if (h->roff.p) (void)hipFree(h->roff.p);
+    if (h->tot) (void)hipFree(h->tot);
     if (h->hot.p) (void)hipFree(h->hot.p);
     marks_reset(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -642,7 +648,7 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
             h->map_passes = (int)value; return KQ_OK;
         }
         case KQ_OPT_KERNEL_SET:
-            if (value < 0 || value > 7) return fail(KQ_ERR_INVALID, "KQ_OPT_KERNEL_SET is a mask of bits 1, 2, 4");
+            if (value < 0 || (value & ~(int64_t)(7 | 16))) return fail(KQ_ERR_INVALID, "KQ_OPT_KERNEL_SET is a mask of bits 1, 2, 4, 16");
             h->kernel_set = (int)value; return KQ_OK;
         case KQ_OPT_OVERLAP:
             if (value < 0 || value > 2) return fail(KQ_ERR_INVALID, "KQ_OPT_OVERLAP must be 0, 1 or 2");
@@ -1089,6 +1095,7 @@ static int pend_add(kq_handle* h, const P3Set& set, int fmt, int aux_fmt) {
     }
     if (!h->d_sets) HIPC(hipMalloc((void**)&h->d_sets, sizeof(P3Set) * P3_MAX_SETS));
     hipLaunchKernelGGL(k_p3set, dim3(1), dim3(1), 0, h->stream, h->d_sets, h->n_pend, set);
+    h->pend_sets[h->n_pend] = set;
     h->pend_fmt = fmt; h->pend_aux_fmt = aux_fmt;
     ++h->n_pend;
     h->pend_records += set.n_max;
@@ -1111,6 +1118,21 @@ static int flush_pending(kq_handle* h) {
     h->stream = work;
     return rc;
 }
+static_assert(ROFF_MAX_SETS == (uint32_t)P3_MAX_SETS, "the offset matrix has a column for every set of a pass");
+// The region-major offset matrix (geometry: kq_roff_host.h) for this pass, or nullptr: the pass then reads the sets' own offset
+// arrays, as it always could.  The buffer is taken at the first pass from what the arena's sizing leaves free, and again only
+// when the table has grown; a failed allocation is not an error.
+static uint32_t* roff_take(kq_handle* h) {
+    for (int i = 0; i < h->n_pend; ++i) if (h->pend_sets[i].n_max >> 32) return nullptr;      // offsets are stored in 32 bits
+    const size_t need = roff_bytes(h->n_alloc_regions());
+    if (!need || !roff_pitch((uint32_t)h->n_pend)) return nullptr;
+    if (h->roff.bytes < need) {
+        if (h->roff.p) { (void)hipFree(h->roff.p); h->roff = DevBuf(); }
+        if (hipMalloc(&h->roff.p, need) != hipSuccess) { (void)hipGetLastError(); h->roff.p = nullptr; return nullptr; }
+        h->roff.bytes = need;
+    }
+    return (uint32_t*)h->roff.p;
+}
 static int flush_pending_base(kq_handle* h) {
     const uint64_t R = h->n_regions;
     int rc = ensure_buf(h->hot, (size_t)(R + 2) * 8);
@@ -1132,9 +1154,31 @@ static int flush_pending_base(kq_handle* h) {
 #define KQ_P3(F) do { \
         hipLaunchKernelGGL((k_count_regions<F, false>), grid, block, 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps); \
         KQ_HOT(F); } while (0)
+    // 4- and 5-byte records: the sets' region offsets are transposed first, the pass reads one row pair per region and adds the
+    // regions' totals to TOT_LINES lines, which k_fold_totals adds to the table state behind it (KQ_OPT_KERNEL_SET bit 16, or no
+    // memory for the matrix: the previous pass -- the sets' own offset arrays, two atomics per region on the table state)
+    Q4SetsRow rows = {};
+    if ((fmt == FMT_TIGHT || fmt == FMT_NARROW) && !(h->kernel_set & 16)) {
+        if (uint32_t* roff = roff_take(h)) {
+            rows.pitch = roff_pitch((uint32_t)h->n_pend);
+            if (!h->tot) {
+                const size_t tb = (size_t)TOT_LINES * 64;
+                if (hipMalloc((void**)&h->tot, tb) != hipSuccess) { (void)hipGetLastError(); h->tot = nullptr; }
+                else HIPC(hipMemsetAsync(h->tot, 0, tb, h->stream));
+            }
+            rows.tot = h->tot;
+            rows.roff = roff - h->reg_lo() * rows.pitch;                 // row r of the geometry (a window allocates its own rows only)
+            for (int i = 0; i < h->n_pend; ++i) { rows.d[i].recs = (const uint32_t*)h->pend_sets[i].recs; rows.d[i].aux = h->pend_sets[i].aux; }
+            const uint64_t n_rows = roff_rows(h->n_alloc_regions());
+            hipLaunchKernelGGL(k_p3_region_offsets, dim3(grid_for(h, n_rows, ROFF_ROWS, 32)), dim3(ROFF_THREADS), 0, h->stream,
+                               roff, h->d_sets, (uint32_t)h->n_pend, rows.pitch, h->reg_lo(), n_rows);
+        }
+    }
 #define KQ_Q4(KC, T) do { \
-        hipLaunchKernelGGL((k_count_regions_q4<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, empty, hot, rps); \
-        KQ_HOT(FMT_NARROW); } while (0)
+        if (rows.roff) hipLaunchKernelGGL((k_count_regions_q4r<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), rows, empty, hot, rps); \
+        else hipLaunchKernelGGL((k_count_regions_q4<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, empty, hot, rps); \
+        KQ_HOT(FMT_NARROW); \
+        if (rows.roff && rows.tot) hipLaunchKernelGGL(k_fold_totals, dim3(1), dim3(256), 0, h->stream, rows.tot, h->st); } while (0)
     // ordinary regions of 4- and 5-byte records: the compact 32-bit-key kernel; skewed ones: the generic folding kernel
     // (pend_aux_fmt == AUX_TIGHT tells it about FMT_TIGHT sets)
     if (fmt == FMT_TIGHT)       { if (h->k == 21) KQ_Q4(21, true); else KQ_Q4(0, true); }
