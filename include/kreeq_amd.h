@@ -389,6 +389,37 @@ int  kq_export_map_images(kq_handle* h, uint16_t map_lo, uint16_t map_hi, void* 
 int  kq_import_map_image(kq_handle* h, uint16_t map, const void* image, uint64_t n_bytes, uint64_t* n_entries,
                          uint64_t* n_tombstones);
 
+/* ---- subgraph (DBG::subgraph, traversal, removeMissingEdges, summary; src/subgraph.cpp) -------------------------------- */
+
+/* The subgraph is a SECOND, ordinary handle `sub` with the k, map_count and device of the database handle `db`: kq_export,
+ * kq_summary (the "Subgraph summary statistics" block, src/subgraph.cpp:163-188), kq_lookup_keys and kq_histogram read it
+ * like any table.  Every call flushes the pending records of both handles first and synchronises.  KQ_ERR_INVALID, before
+ * any device work, for null pointers, db == sub, a windowed handle (KQ_OPT_BUCKET_WINDOW / KQ_OPT_SHARD_WINDOW), unknown
+ * flag bits and a depth outside 0..255; KQ_ERR_MISMATCH for handles that differ in k / map_count / device; the handles
+ * stay usable after a refusal.
+ *
+ * kq_subgraph_seed(_dev)  Replaces DBGsubgraphFromSegment for every segment of the batch + mergeSubgraphs (:190-288, :42-112).
+ *     The batch is cut into segments (ACGT runs) like kq_lookup_sequence cuts it.  Within ONE segment every canonical key counts
+ *     once, and its first position decides: a key of the database adds its logical entry (exact 32-bit counters of either
+ *     tier); an absent key adds, unless flags has KQ_SUBGRAPH_NO_REFERENCE, a constructed k-mer with cov 1 and the at most
+ *     two edges its neighbours inside the segment at that position give (the edge rule of a count).  Segments ADD UP (a key of
+ *     m segments holds m times its counters, saturating at 2^32 - 1), and so do calls: seeding two batches == seeding their
+ *     concatenation with a separator.  The result does not depend on the launch geometry.  Batches below 2^32 - 1 bytes;
+ *     device scratch: 25 to 33 bytes per base of the batch, freed before the call returns.  The _dev variant takes a device pointer valid on the handles' GPU.
+ * kq_subgraph_expand      Replaces DBG::traversal (:301-415) for one resident map range: `depth` rounds; round 1 starts from the
+ *     k-mers of `sub`, round r + 1 from those round r found; every edge counter != 0 of a frontier k-mer gives a neighbour
+ *     (DBG::buildNextKmer, :581-597), which is found when it is not in `sub` and is in `db`.  What was found is inserted, with
+ *     its database entry, after the last round.  The frontier stays on the device; its size returns to the host once per
+ *     round, and an empty one ends the rounds.  *n_added = k-mers inserted.  KQ_ERR_TABLE_FULL when the frontier list, the
+ *     visited set or `sub` cannot grow.
+ * kq_subgraph_trim        Replaces DBG::removeMissingEdges (:599-625): every edge counter > cov_cutoff of `sub` whose neighbour
+ *     k-mer is not in `sub` becomes 0, in both tiers; counters <= cov_cutoff are not examined.  Not to be mixed with inserts. */
+enum { KQ_SUBGRAPH_NO_REFERENCE = 1 };
+int  kq_subgraph_seed(kq_handle* db, kq_handle* sub, const char* bases, uint64_t len, uint32_t flags);
+int  kq_subgraph_seed_dev(kq_handle* db, kq_handle* sub, const char* d_bases, uint64_t len, uint32_t flags);
+int  kq_subgraph_expand(kq_handle* db, kq_handle* sub, int depth, uint64_t* n_added);
+int  kq_subgraph_trim(kq_handle* sub, uint32_t cov_cutoff);
+
 #ifdef __cplusplus
 }
 #endif

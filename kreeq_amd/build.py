@@ -1,7 +1,7 @@
 """In-tree build of the native pieces (no JIT cache: the .so/.bin travel with the repo snapshot).
 
   kreeq_amd/lib/libkreeq_amd.so   HIP kernels + C ABI (include/kreeq_amd.h), gfx950 only
-  kreeq_amd/bin/kreeq             host CLI clone (validate / union), links the library above
+  kreeq_amd/bin/kreeq             host CLI clone (validate / union / subgraph), links the library above
 """
 import os
 import shutil
@@ -14,7 +14,7 @@ CLI = os.path.join(PKG, "bin", "kreeq")
 HOSTLIB = os.path.join(PKG, "lib", "libkreeq_host.so")       # .kreeq database files for the multi-GPU driver (no GPU code)
 
 HIP_SOURCES = [os.path.join(PKG, "csrc", "kreeq_amd.hip")]
-HIP_DEPS = HIP_SOURCES + [os.path.join(PKG, "csrc", f) for f in ("kq_device.h", "kq_partition.h", "kq_kernels.h", "kq_fastx.h", "kq_dbimage.h", "kq_dbimage_host.h", "kq_roff_host.h")] + [os.path.join(ROOT, "include", "kreeq_amd.h")]
+HIP_DEPS = HIP_SOURCES + [os.path.join(PKG, "csrc", f) for f in ("kq_device.h", "kq_partition.h", "kq_kernels.h", "kq_fastx.h", "kq_dbimage.h", "kq_dbimage_host.h", "kq_roff_host.h", "kq_subgraph.h")] + [os.path.join(ROOT, "include", "kreeq_amd.h")]
 HOST_DIR = os.path.join(PKG, "host")
 
 

@@ -17,9 +17,10 @@ SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profi
            "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
            "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_lookup_keys", "kq_branch_scan", "kq_merge", "kq_import", "kq_export",
-           "kq_export_map_images", "kq_import_map_image"]
+           "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_trim"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
+SUBGRAPH_NO_REFERENCE = 1                # KQ_SUBGRAPH_NO_REFERENCE
 
 
 class KqError(RuntimeError):
@@ -131,6 +132,10 @@ def load():
     L.kq_export.argtypes = [vp, u16, u16, vp, u64, C.POINTER(u64)]
     L.kq_export_map_images.argtypes = [vp, u16, u16, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.kq_import_map_image.argtypes = [vp, u16, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.kq_subgraph_seed.argtypes = [vp, vp, vp, u64, u32]
+    L.kq_subgraph_seed_dev.argtypes = [vp, vp, vp, u64, u32]
+    L.kq_subgraph_expand.argtypes = [vp, vp, ci, C.POINTER(u64)]
+    L.kq_subgraph_trim.argtypes = [vp, u32]
     _lib = L
     return L
 
@@ -406,3 +411,33 @@ class KreeqDB:
         n, t = C.c_uint64(0), C.c_uint64(0)
         _check(load().kq_import_map_image(self._h, map_index, _p(buf), len(buf), C.byref(n), C.byref(t)))
         return n.value, t.value
+
+    # -- subgraph (reference src/subgraph.cpp): `sub` is a second KreeqDB with this one's k, map_count and device
+    def subgraph_seed(self, sub, bases: bytes, no_reference=False):
+        """adds the k-mers of a sequence batch (segments = ACGT runs) to `sub`: database entries, or constructed k-mers"""
+        buf = np.frombuffer(bases, dtype=np.uint8)
+        _check(load().kq_subgraph_seed(self._h, sub._h, _p(buf) if len(buf) else None, len(buf), SUBGRAPH_NO_REFERENCE if no_reference else 0))
+
+    def subgraph_seed_dev(self, sub, bases_ptr, n, no_reference=False):
+        _check(load().kq_subgraph_seed_dev(self._h, sub._h, C.c_void_p(bases_ptr), n, SUBGRAPH_NO_REFERENCE if no_reference else 0))
+
+    def subgraph_expand(self, sub, depth):
+        """`depth` rounds of the traversal from the k-mers of `sub` through this database; -> k-mers added"""
+        n = C.c_uint64(0)
+        _check(load().kq_subgraph_expand(self._h, sub._h, depth, C.byref(n)))
+        return n.value
+
+    def subgraph_trim(self, cov_cutoff=0):
+        """clears the edge counters > cov_cutoff of THIS table (a subgraph) that lead to k-mers outside it"""
+        _check(load().kq_subgraph_trim(self._h, cov_cutoff))
+
+    def subgraph(self, seq: bytes, depth, algorithm="traversal", no_reference=False, cov_cutoff=0):
+        """seed + expand + trim -> the subgraph as a new KreeqDB.  Only the traversal runs through this binding (best-first is
+        the CLI's: `kreeq subgraph`)."""
+        if algorithm != "traversal":
+            raise ValueError(f"algorithm {algorithm!r}: only 'traversal' is available here (best-first: the kreeq CLI)")
+        sub = KreeqDB(self.k, self.map_count, self.device, capacity_hint=len(seq) + 1024)
+        self.subgraph_seed(sub, seq, no_reference)
+        self.subgraph_expand(sub, depth)
+        sub.subgraph_trim(cov_cutoff)
+        return sub

@@ -27,6 +27,7 @@ using namespace kq;
 #include "kq_kernels.h"
 #include "kq_fastx.h"
 #include "kq_dbimage.h"
+#include "kq_subgraph.h"
 
 // ================================================================================================
 // host side
@@ -2457,6 +2458,179 @@ int kq_import_map_image(kq_handle* h, uint16_t map, const void* image, uint64_t 
     if (rc) return rc;
     *n_entries = res.n_entries; *n_tombstones = res.n_tombstones;
     return KQ_OK;
+}
+
+// ---- subgraph mode (kq_subgraph.h; reference src/subgraph.cpp) --------------------------------------------------------
+// the checks every subgraph entry point makes before any device work
+static int sg_check(kq_handle* db, kq_handle* sub) {
+    if (!db || !sub) return fail(KQ_ERR_INVALID, "null handle");
+    if (db == sub) return fail(KQ_ERR_INVALID, "the subgraph needs a handle of its own (db == sub)");
+    if (db->windowed || sub->windowed) return fail(KQ_ERR_INVALID, "subgraph calls do not take a windowed handle (KQ_OPT_BUCKET_WINDOW / KQ_OPT_SHARD_WINDOW)");
+    if (db->k != sub->k || db->map_count != sub->map_count || db->device != sub->device)
+        return fail(KQ_ERR_MISMATCH, "handles differ in k / map_count / device");
+    return KQ_OK;
+}
+// both tables as they are after everything counted so far; the database's stream has drained, the work goes to sub's
+static int sg_begin(kq_handle* db, kq_handle* sub) {
+    HIPC(hipSetDevice(sub->device));
+    { int frc = flush_pending(sub); if (frc) return frc; }
+    { int frc = flush_pending(db); if (frc) return frc; }
+    materialize(db);
+    int rc = kq_sync(db);
+    if (rc) return rc;
+    materialize(sub);
+    return KQ_OK;
+}
+static uint64_t pow2_at_least(uint64_t n) { uint64_t c = 1024; while (c < n) c *= 2; return c; }
+
+int kq_subgraph_seed_dev(kq_handle* db, kq_handle* sub, const char* d_bases, uint64_t len, uint32_t flags) {
+    int rc = sg_check(db, sub);
+    if (rc) return rc;
+    if (!d_bases && len) return fail(KQ_ERR_INVALID, "null sequence");
+    if (flags & ~1u) return fail(KQ_ERR_INVALID, "unknown flags 0x%x", flags);
+    if (len >= 0xFFFFFFFFull) return fail(KQ_ERR_INVALID, "sequence batch of %llu bytes: seed in batches below 2^32 - 1 bytes", (unsigned long long)len);
+    rc = sg_begin(db, sub);
+    if (rc) return rc;
+    const int k = db->k;
+    if (len < (uint64_t)k) return KQ_OK;
+    hipStream_t st = sub->stream;
+    const uint64_t n_pos = len - (uint64_t)k + 1, set_size = pow2_at_least(2 * n_pos);
+    DevPtrs mem;
+    uint32_t *d_flag = nullptr, *d_seg = nullptr, *d_set = nullptr;
+    uint64_t* d_key = nullptr; uint8_t* d_info = nullptr; void* d_tmp = nullptr;
+    struct Res { SgSeedOut out; unsigned int err, pad; } res;
+    Res* d_res = nullptr;
+    size_t tmp_bytes = 0;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_flag, d_seg, (int64_t)len, st) != hipSuccess) return fail(KQ_ERR_HIP, "segment scan setup failed");
+    if (mem.alloc((void**)&d_flag, len * 4) != hipSuccess || mem.alloc((void**)&d_seg, len * 4) != hipSuccess || mem.alloc((void**)&d_key, n_pos * 8) != hipSuccess ||
+        mem.alloc((void**)&d_info, n_pos) != hipSuccess || mem.alloc((void**)&d_set, set_size * 4) != hipSuccess || mem.alloc(&d_tmp, tmp_bytes) != hipSuccess ||
+        mem.alloc((void**)&d_res, sizeof(Res)) != hipSuccess)
+        return fail(KQ_ERR_NOMEM, "no device memory for the seed scratch of %llu bases", (unsigned long long)len);
+    const uint8_t* ab; uint64_t lead;
+    aligned_view(d_bases, &ab, &lead);
+    HIPC(hipMemsetAsync(d_key, 0xFF, n_pos * 8, st));
+    HIPC(hipMemsetAsync(d_set, 0xFF, set_size * 4, st));
+    HIPC(hipMemsetAsync(d_res, 0, sizeof(Res), st));
+    hipLaunchKernelGGL(k_sg_invalid, dim3(grid_for(sub, len, 256)), dim3(256), 0, st, (const uint8_t*)d_bases, len, d_flag);
+    HIPC(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flag, d_seg, (int64_t)len, st));
+    hipLaunchKernelGGL(k_sg_keys, dim3(grid_for(sub, n_tiles_of(lead, len), 1, 32)), dim3(TILE_THREADS), 0, st, ab, lead, len, k, d_key, d_info);
+    hipLaunchKernelGGL(k_sg_first, dim3(grid_for(sub, n_pos, 256)), dim3(256), 0, st, d_key, d_seg, n_pos, d_set, set_size - 1, &d_res->err);
+    // what the winners will add, so that the table grows before they do
+    hipLaunchKernelGGL(k_sg_seed_add<false>, dim3(grid_for(sub, set_size, 256)), dim3(256), 0, st, db->view(), sub->view(), d_set, set_size, d_key, d_info,
+                       flags & 1u, &d_res->out);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (res.err) return fail(KQ_ERR_HIP, "seed: the (segment, k-mer) set overflowed");      // cannot happen: the set has two slots per position
+    if (!res.out.n_kmers) return KQ_OK;
+    rc = reserve(sub, res.out.n_kmers, res.out.n_instances);
+    if (rc) return rc;
+    sub->table_empty = false;
+    hipLaunchKernelGGL(k_sg_seed_add<true>, dim3(grid_for(sub, set_size, 256)), dim3(256), 0, st, db->view(), sub->view(), d_set, set_size, d_key, d_info,
+                       flags & 1u, &d_res->out);
+    HIPC(hipGetLastError());
+    return kq_sync(sub);
+}
+int kq_subgraph_seed(kq_handle* db, kq_handle* sub, const char* bases, uint64_t len, uint32_t flags) {
+    int rc = sg_check(db, sub);
+    if (rc) return rc;
+    if (!bases && len) return fail(KQ_ERR_INVALID, "null sequence");
+    if (flags & ~1u) return fail(KQ_ERR_INVALID, "unknown flags 0x%x", flags);
+    HIPC(hipSetDevice(sub->device));
+    void* d = nullptr;
+    rc = stage_in(sub, bases, len, &d);
+    if (rc) return rc;
+    return kq_subgraph_seed_dev(db, sub, (const char*)d, len, flags);
+}
+
+int kq_subgraph_expand(kq_handle* db, kq_handle* sub, int depth, uint64_t* n_added) {
+    int rc = sg_check(db, sub);
+    if (rc) return rc;
+    if (!n_added) return fail(KQ_ERR_INVALID, "null n_added");
+    if (depth < 0 || depth > 255) return fail(KQ_ERR_INVALID, "search depth %d outside 0..255", depth);      // uint8_t in the reference (src/subgraph.cpp:307)
+    *n_added = 0;
+    rc = sg_begin(db, sub);
+    if (rc) return rc;
+    rc = check_errors(sub);
+    if (rc) return rc;
+    const uint64_t n_seed = sub->st_host->slots_used;
+    if (!depth || !n_seed) return KQ_OK;
+    hipStream_t st = sub->stream;
+    DevPtrs mem;
+    SgExpandState state{};
+    SgExpandState* d_state = nullptr;
+    kq_entry* d_ents = nullptr; uint64_t* d_vis = nullptr;
+    uint64_t ents_cap = 0, vis_size = 0;
+    // room for a round that finds 8 k-mers per frontier k-mer: the found list and the visited set (load <= 1/2) double like a table
+    auto make_room = [&](uint64_t n_ents, uint64_t frontier) -> int {
+        const uint64_t need = n_ents + 8 * frontier;
+        if (need > ents_cap) {
+            uint64_t cap = std::max<uint64_t>(ents_cap, 1024);
+            while (cap < need) cap *= 2;
+            kq_entry* fresh = nullptr;
+            if (mem.alloc((void**)&fresh, cap * sizeof(kq_entry)) != hipSuccess) return fail(KQ_ERR_TABLE_FULL, "cannot grow the frontier list to %llu k-mers: out of device memory", (unsigned long long)cap);
+            if (n_ents && d_ents) HIPC(hipMemcpyAsync(fresh, d_ents, n_ents * sizeof(kq_entry), hipMemcpyDeviceToDevice, st));
+            HIPC(hipStreamSynchronize(st));
+            mem.release(d_ents);
+            d_ents = fresh; ents_cap = cap;
+        }
+        const uint64_t vis_need = 2 * (need - n_seed);
+        if (vis_need > vis_size) {
+            const uint64_t size = pow2_at_least(std::max(vis_need, 2 * vis_size));
+            HIPC(hipStreamSynchronize(st));
+            mem.release(d_vis);
+            if (mem.alloc((void**)&d_vis, size * 8) != hipSuccess) { d_vis = nullptr; vis_size = 0; return fail(KQ_ERR_TABLE_FULL, "cannot grow the visited set to %llu slots: out of device memory", (unsigned long long)size); }
+            vis_size = size;
+            HIPC(hipMemsetAsync(d_vis, 0xFF, size * 8, st));
+            if (n_ents > n_seed) hipLaunchKernelGGL(k_sg_visited_fill, dim3(grid_for(sub, n_ents - n_seed, 256)), dim3(256), 0, st, d_ents, n_seed, n_ents, d_vis, size - 1, d_state);
+        }
+        return KQ_OK;
+    };
+    if (mem.alloc((void**)&d_state, sizeof(SgExpandState)) != hipSuccess) return fail(KQ_ERR_NOMEM, "no device memory");
+    rc = make_room(n_seed, n_seed);
+    if (rc) return rc;
+    // the seeds with their subgraph entries: the first frontier (the counter of k_export becomes n_ents)
+    HIPC(hipMemsetAsync(d_state, 0, sizeof(SgExpandState), st));
+    hipLaunchKernelGGL(k_export, dim3(grid_for(sub, sub->n_slots(), 1024)), dim3(256), 0, st, sub->view(), (uint32_t)sub->map_count, 0u, (uint32_t)sub->map_count,
+                       d_ents, ents_cap, &d_state->n_ents);
+    HIPC(hipGetLastError());
+    uint64_t f_lo = 0, f_hi = n_seed;
+    for (int round = 0; round < depth && f_hi > f_lo; ++round) {
+        rc = make_room(f_hi, f_hi - f_lo);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_sg_expand, dim3(grid_for(sub, (f_hi - f_lo) * 8, 256)), dim3(256), 0, st, db->view(), sub->view(), d_ents, f_lo, f_hi, ents_cap,
+                           d_vis, vis_size - 1, d_state);
+        HIPC(hipGetLastError());
+        // only the size of the next frontier returns to the host
+        HIPC(hipMemcpyAsync(&state, d_state, sizeof state, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        if (state.err) return fail(KQ_ERR_HIP, "expand: frontier list or visited set overflowed (%u)", state.err);      // cannot happen: make_room
+        if (round == 0 && state.n_ents < n_seed) return fail(KQ_ERR_HIP, "expand: %llu of %llu seeds listed", (unsigned long long)state.n_ents, (unsigned long long)n_seed);
+        f_lo = f_hi; f_hi = state.n_ents;
+    }
+    const uint64_t n_found = f_hi - n_seed;
+    if (n_found) {                                   // after the last round: the seed set was "seeds only" throughout (src/subgraph.cpp:321)
+        rc = reserve(sub, n_found, state.n_instances);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_import, dim3(grid_for(sub, n_found, 256)), dim3(256), 0, st, sub->view(), (const kq_entry*)(d_ents + n_seed), n_found);
+        HIPC(hipGetLastError());
+        rc = kq_sync(sub);
+        if (rc) return rc;
+    }
+    *n_added = n_found;
+    return KQ_OK;
+}
+
+int kq_subgraph_trim(kq_handle* sub, uint32_t cov_cutoff) {
+    if (!sub) return fail(KQ_ERR_INVALID, "null handle");
+    if (sub->windowed) return fail(KQ_ERR_INVALID, "subgraph calls do not take a windowed handle (KQ_OPT_BUCKET_WINDOW / KQ_OPT_SHARD_WINDOW)");
+    HIPC(hipSetDevice(sub->device));
+    int rc = flush_pending(sub);
+    if (rc) return rc;
+    materialize(sub);
+    hipLaunchKernelGGL(k_sg_trim, dim3(grid_for(sub, sub->n_slots(), 256)), dim3(256), 0, sub->stream, sub->view(), cov_cutoff);
+    HIPC(hipGetLastError());
+    return kq_sync(sub);
 }
 
 }  // extern "C"

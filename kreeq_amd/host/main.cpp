@@ -1,4 +1,4 @@
-// kreeq (MI355X build) -- host CLI with the reference's `validate` / `union` interface.
+// kreeq (MI355X build) -- host CLI with the reference's `validate` / `union` / `subgraph` interface.
 // Flag names, stdout blocks, exit codes and the .kreeq directory follow vgl-hub/kreeq @ 2024_08_07
 // (src/main.cpp:78-97, :220-229; src/input.cpp:76-152; src/kreeq-output.cpp:34-136;
 // src/graph-builder.cpp:288-293; src/kreeq.cpp:78-106).  All compute goes through the C ABI
@@ -28,6 +28,7 @@
 #include "fastx.h"
 #include "kreeq_amd.h"
 #include "kreeq_db.h"
+#include "subgraph.h"
 #include "variants.h"
 
 using namespace kqhost;
@@ -37,7 +38,7 @@ namespace {
 const char* kVersion = "0.1.0-mi355x";
 
 struct UserInput {                       // reference UserInputKreeq (include/input.h:25-34) + gfalibs UserInput fields used
-    int mode = 0;                        // 0 validate, 1 union
+    int mode = 0;                        // 0 validate, 1 union, 2 subgraph
     std::string inSequence, outFile, prefix = ".", inBedInclude;
     std::vector<std::string> inReads, kmerDB;
     int kmerLen = 21;
@@ -46,6 +47,8 @@ struct UserInput {                       // reference UserInputKreeq (include/in
     double maxMem = 0;
     int device = 0;
     int passes = 0;                      // --passes: count the maps in this many ranges (memory-bounded mode); 0 = as many as the HBM asks for
+    std::string travAlgorithm = "best-first";      // subgraph (include/input.h:32)
+    int noCollapse = 0, noReference = 0;
 };
 
 int verbose_flag = 0, cmd_flag = 0;
@@ -140,6 +143,7 @@ void print_help() {
     printf("\nModes:\n");
     printf("validate\n");
     printf("union\n");
+    printf("subgraph\n");
     exit(0);
 }
 
@@ -877,6 +881,58 @@ int run(UserInput& ui) {
             verbose("Peak host memory: " + std::to_string(peak_rss_mb()) + " MB");
             break;
         }
+        case 2: {                                                    // src/input.cpp:153-181
+            // loadGraph: the whole database in one resident table (the reference's traversal changes its frontier between map
+            // ranges, which is not restated: DESIGN.md section 12)
+            DbSource db(ui.kmerDB[0]);
+            verbose("Overriding default kmer length (" + std::to_string(ui.kmerLen) + ") with DB kmer length (" + std::to_string(db.idx.k) + ").");
+            e.k = db.idx.k; e.map_count = db.idx.map_count;
+            const uint64_t bound = db.entries_bound(0, e.map_count);
+            if (passes_for(ui, bound) > 1)
+                die("Error: the database (<= " + std::to_string(bound) + " k-mers) does not fit the device memory in one table; subgraph does not run in map ranges");
+            e.create(bound + 1024);
+            const uint64_t n_in = db.import_into(e.h, 0, e.map_count);
+            verbose("Database loaded (" + std::to_string(n_in) + " k-mers)");
+            if (!ui.inSequence.empty()) {
+                verbose("Loading input sequences");
+                load_genome(ui.inSequence, e.genome);
+                verbose("Sequences loaded");
+            }
+            auto step = [t0 = now_s()](const char* what) mutable {      // KQ_SUBGRAPH_TRACE=1: wall clock of the steps to stderr
+                static const bool on = [] { const char* v = getenv("KQ_SUBGRAPH_TRACE"); return v && atoi(v) != 0; }();
+                const double t1 = now_s();
+                if (on) fprintf(stderr, "[subgraph] %s: %.3f s\n", what, t1 - t0);
+                t0 = t1;
+            };
+            kq_handle* sub = nullptr;
+            kq_or_die(kq_create(&sub, ui.device, e.k, e.map_count, e.genome.joined.size() + 1024));
+            verbose("Subsetting graph");                                 // DBG::subgraph, src/subgraph.cpp:116-161
+            kq_or_die(kq_subgraph_seed(e.h, sub, e.genome.joined.data(), e.genome.joined.size(), ui.noReference ? KQ_SUBGRAPH_NO_REFERENCE : 0));
+            step("seed");
+            verbose("Searching graph");                                  // DBG::searchGraph, :290-299; default depths: include/kreeq.h:171-175
+            const bool best_first = ui.travAlgorithm == "best-first";
+            const int depth = ui.kmerDepth != -1 ? ui.kmerDepth : best_first ? e.k : (e.k + 1) / 2;
+            uint64_t n_added = 0;
+            if (best_first) n_added = subgraph_best_first(e.h, sub, e.k, e.map_count, depth, ui.covCutOff, [](const std::string& m) { verbose(m); });
+            else kq_or_die(kq_subgraph_expand(e.h, sub, depth, &n_added));
+            step("expand");
+            verbose(std::to_string(n_added) + " k-mers added by the search");
+            verbose("Remove missing edges");                             // DBG::removeMissingEdges, :599-628
+            kq_or_die(kq_subgraph_trim(sub, ui.covCutOff));
+            step("trim");
+            kq_stats st;
+            kq_or_die(kq_summary(sub, &st));
+            std::cout << "Subgraph summary statistics:\n"                // DBG::summary(ParallelMap32color&), :163-188
+                      << "Total kmers: " << st.total << "\n"
+                      << "Unique kmers: " << st.unique << "\n"
+                      << "Distinct kmers: " << st.distinct << "\n"
+                      << "Missing kmers: " << st.missing << "\n"
+                      << "Total edges: " << st.edges << "\n";
+            kq_destroy(sub);
+            // (the reference prints gfalibs' "+++Assembly summary+++" of the GFA model here: not built)
+            e.stats();                                                   // DBG::report with no -o, src/kreeq-output.cpp:34-60
+            break;
+        }
         default:
             fprintf(stderr, "Invalid mode.\n");
             exit(1);
@@ -967,7 +1023,7 @@ int main(int argc, char** argv) {
     }
     if (mode == "validate") ui.mode = 0;
     else if (mode == "union") ui.mode = 1;
-    else if (mode == "subgraph") { fprintf(stderr, "mode subgraph is not part of this build (validate / union only)\n"); return EXIT_FAILURE; }
+    else if (mode == "subgraph") ui.mode = 2;
     else { fprintf(stderr, "mode %s does not exist. Terminating\n", argv[1]); return EXIT_FAILURE; }
 
     if (ui.mode == 0) {
@@ -1037,6 +1093,69 @@ int main(int argc, char** argv) {
             }
         }
         if (ui.kmerLen < 2 || ui.kmerLen > 32) { fprintf(stderr, "Invalid kmer length.\n"); return EXIT_FAILURE; }
+    } else if (ui.mode == 2) {
+        static struct option long_options[] = {                      // src/main.cpp:298-315
+            {"coverage-cutoff", required_argument, 0, 'c'}, {"database", required_argument, 0, 'd'},
+            {"input-sequence", required_argument, 0, 'f'}, {"traversal-algorithm", required_argument, 0, 0},
+            {"search-depth", required_argument, 0, 0}, {"no-collapse", no_argument, &ui.noCollapse, 1},
+            {"no-reference", no_argument, &ui.noReference, 1}, {"out-format", required_argument, 0, 'o'},
+            {"input-positions", required_argument, 0, 'p'}, {"threads", required_argument, 0, 'j'},
+            {"max-memory", required_argument, 0, 'm'}, {"device", required_argument, 0, 0},
+            {"verbose", no_argument, &verbose_flag, 1}, {"cmd", no_argument, &cmd_flag, 1},
+            {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+        for (;;) {
+            int option_index = 1;
+            int c = getopt_long(argc, argv, "-:c:d:f:j:m:o:p:h", long_options, &option_index);
+            if (c == -1) break;
+            switch (c) {
+                case ':': fprintf(stderr, "option -%c is missing a required argument\n", optopt); return EXIT_FAILURE;
+                case 0:
+                    if (strcmp(long_options[option_index].name, "search-depth") == 0) ui.kmerDepth = atoi(optarg);
+                    if (strcmp(long_options[option_index].name, "traversal-algorithm") == 0) ui.travAlgorithm = optarg;
+                    if (strcmp(long_options[option_index].name, "device") == 0) ui.device = atoi(optarg);
+                    break;
+                case 'c':
+                    if (!is_number(optarg)) { fprintf(stderr, "input '%s' to option -%c must be a number\n", optarg, optopt); return EXIT_FAILURE; }
+                    ui.covCutOff = (uint32_t)atoi(optarg);
+                    break;
+                case 'd':
+                    optind--;
+                    for (; optind < argc && *argv[optind] != '-' && !is_int(argv[optind]); optind++) {
+                        if_file_exists(argv[optind]);
+                        ui.kmerDB.push_back(argv[optind]);
+                    }
+                    break;
+                case 'f': if_file_exists(optarg); ui.inSequence = optarg; break;
+                case 'o': ui.outFile = optarg; break;
+                case 'p': if_file_exists(optarg); ui.inBedInclude = optarg; break;
+                case 'j': ui.maxThreads = atoi(optarg); break;
+                case 'm': ui.maxMem = atof(optarg); break;
+                case 'h':
+                    printf("kreeq subgraph [options]\n\nOptions:\n");
+                    printf("\t-c --coverage-cutoff exclude nodes and edges below or equal to the cutoff (default: 0).\n");
+                    printf("\t-d --database DBG database.\n");
+                    printf("\t-f --input-sequence sequence input file (fasta).\n");
+                    printf("\t--traversal-algorithm <string> the approach used for graph search (best-first/traversal, default: best-first).\n");
+                    printf("\t--search-depth the max depth for graph traversal (default: k for best-first, ceil(k / 2) for traversal; traversal: at most 255).\n");
+                    printf("\t--no-collapse accepted; no effect (the GFA model and its linear-node collapse are not built).\n");
+                    printf("\t--no-reference do not include reference nodes (default: false).\n");
+                    printf("\t-o --out-format not supported by this build (the GFA writer is not built): refused.\n");
+                    printf("\t-p --input-positions not supported by this build: refused.\n");
+                    printf("\t-j --threads <n> accepted for compatibility.\n");
+                    printf("\t-m --max-memory <GB> HBM the database table may use (default: 60 %% of what is free).\n");
+                    printf("\t--device <n> GPU to use (default 0).\n");
+                    printf("\t--cmd print $0 to stdout.\n");
+                    exit(0);
+                default: break;
+            }
+        }
+        if (ui.kmerDB.size() != 1) { fprintf(stderr, "Need to provide one database (-d).\n"); return EXIT_FAILURE; }   // src/main.cpp:413-416
+        if (!ui.inBedInclude.empty()) { fprintf(stderr, "Error: -p / --input-positions is not supported by this build (BED paths to segments are not built).\n"); return EXIT_FAILURE; }
+        if (!ui.outFile.empty()) { fprintf(stderr, "Error: -o %s: subgraph output files (GFA) are not supported by this build; the summary goes to stdout.\n", ui.outFile.c_str()); return EXIT_FAILURE; }
+        if (ui.travAlgorithm != "best-first" && ui.travAlgorithm != "traversal") {       // src/subgraph.cpp:296
+            fprintf(stderr, "Cannot find input algorithm (%s). Terminating.\n", ui.travAlgorithm.c_str());
+            return EXIT_FAILURE;
+        }
     } else {
         static struct option long_options[] = {                      // src/main.cpp:220-229
             {"databases", required_argument, 0, 'd'}, {"out-format", required_argument, 0, 'o'},
