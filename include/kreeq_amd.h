@@ -159,7 +159,11 @@ void* kq_get_stream(kq_handle* h);
  *                          with k_lv_scatter (round 2's) instead of k_lv_scatter_s, 16 = the table pass of 4- and 5-byte records with
  *                          k_count_regions_q4 (every wave reads its region's offsets from the sets' own offset arrays, through the
  *                          descriptors in memory, and the region's totals go to the table state with two atomics per region) instead of
- *                          k_p3_region_offsets + k_count_regions_q4r + k_fold_totals.  (8 is not assigned.)  Default 0. */
+ *                          k_p3_region_offsets + k_count_regions_q4r + k_fold_totals, 32 = the last split level of a plan with a middle
+ *                          level through the unit path (k_lv_hist + offsets + scans + k_lv_scatter_s) also where the slice's even
+ *                          buckets would select k_lv_segment_s (one workgroup per sub-bucket segment), 64 = k_lv_segment_s wherever
+ *                          it applies, whatever the buckets look like and also in passes that do not read them back (tests,
+ *                          measurement).  (8 is not assigned.)  Default 0. */
 enum { KQ_OPT_TRUST_CAPACITY = 1, KQ_OPT_COUNT_PATH = 2, KQ_OPT_SLICE_KMERS = 3, KQ_OPT_COUNT_MAP_RANGE = 4, KQ_OPT_PROFILE = 5,
        KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13, KQ_OPT_SHARD_WINDOW = 14,
        KQ_OPT_TEST_FAIL_PLAN = 100 /* failure-path tests only: the next partition plan of a count fails with KQ_ERR_NOMEM */ };

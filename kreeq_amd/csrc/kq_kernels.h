@@ -656,6 +656,148 @@ __global__ __launch_bounds__(LV_THREADS, TIGHT ? KQ_LVS_OCC_TIGHT : KQ_LVS_OCC) 
         }
     }
 }
+// The last level (narrow records in, tight records out) of a plan with a middle level, one workgroup per SEGMENT instead of per unit: a
+// record of segment s lands inside [seg_off[s], seg_off[s + 1]) of the output, so the workgroup that owns the whole segment counts its bins
+// itself (u32 array only, the quad loads of k_lv_hist<FMT_NARROW>), writes the segment's region offsets gb[s * nb + bin] = seg_off[s] +
+// prefix, and splits the segment with the round body of k_lv_scatter_s<true>, the bins' cursors in registers from the first round to the
+// last.  No unit table, no (unit, bin) matrix, no scan over all groups; the second read of the segment follows its first within one
+// workgroup's lifetime.  gb[0 .. n_seg * nb] ends as run_level leaves it.  Any segment size is correct (0 records: offsets only); a segment
+// far above the mean is one long workgroup, which is why the host takes this kernel only for slices with even buckets (kq_seg_gate_host.h).
+// KQ_LVG_BACK: the rounds run from the segment's end to its start (the lines counted last are re-read first) instead of front to back.
+// Measured at 3 Gbp (16 384 segments of ~40 000 records, 207 bins), old and new alternating in one process: front to back 1.83 ms per
+// slice and range, back to front 1.89 ms, the unit path 2.26 - 2.29 ms (profiles/r05/).  Front to back ships.
+#ifndef KQ_LVG_BACK
+#define KQ_LVG_BACK 0
+#endif
+__global__ __launch_bounds__(LV_THREADS, KQ_LVS_OCC_TIGHT) void k_lv_segment_s(const uint32_t* __restrict__ recs32, const uint8_t* __restrict__ recs_aux, LevelCfg lv,
+                                                           const unsigned long long* __restrict__ seg_off, unsigned long long* __restrict__ gb,
+                                                           uint32_t* __restrict__ out) {
+    constexpr int NC = 512;
+    constexpr bool BACK = KQ_LVG_BACK != 0;
+    static_assert(LV_THREADS == NC && LV_ITEMS == 8, "one counter per thread");
+    __shared__ uint64_t s_buf[LV_TILE];
+    __shared__ uint32_t s_hist[2][NC], s_loff[NC + 1], s_grel[NC], s_wave[LV_THREADS / 64], s_rst[NC];
+    const int tid = threadIdx.x;
+    const uint32_t nb = lv.nb, rs = lv.rep_shift, n_ctr = (nb + 1) << rs;      // (nb + 1) << rs <= NC (host)
+    const uint32_t sub = (uint32_t)tid & ((1u << rs) - 1u), my_bin = (uint32_t)tid >> rs;
+    const bool own_bin = sub == 0 && my_bin < nb;                       // this thread's counter is the first of bin my_bin
+    const uint32_t b = blockIdx.x;                                      // the segment; spb == 1 (host)
+    const uint64_t lo = seg_off[b], hi = seg_off[b + 1];
+    {
+        const uint32_t first = (b >> lv.nr_shift) * lv.nr_rps + (b & ((1u << lv.nr_shift) - 1u)) * lv.nr_sub;      // narrow_bin's origin; nr_div == 1
+        if ((uint32_t)tid < nb) s_rst[tid] = lv.rstart[first + tid];
+    }
+    s_hist[0][tid] = 0;
+    s_hist[1][tid] = 0;
+    __syncthreads();
+    // count pass: the segment's bins into the replicated counters of s_hist[1] (k_lv_hist<FMT_NARROW>: 16-byte loads at absolute quad
+    // indices, the quads at the segment's ends masked per element; the array is 16-byte aligned with slack behind its last record)
+    {
+        const uint4* v4 = reinterpret_cast<const uint4*>(recs32);
+        const uint64_t q0 = lo >> 2, q1 = hi > lo ? (hi + 3) >> 2 : q0;
+        for (uint64_t qb = q0; qb < q1; qb += 4ull * LV_THREADS) {
+            uint4 q[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) q[j] = v4[min(qb + (uint64_t)j * LV_THREADS + tid, q1 - 1)];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint64_t qi = qb + (uint64_t)j * LV_THREADS + tid;
+                const uint32_t e[4] = {q[j].x, q[j].y, q[j].z, q[j].w};
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const uint64_t ri = 4 * qi + c;
+                    if (qi < q1 && ri >= lo && ri < hi) atomicAdd(&s_hist[1][(narrow_bin(lv, b, e[c]) << rs) | sub], 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // exclusive scan of the bins' counts (the first counter's thread of a bin adds up its replicas) -> region offsets and cursors
+    uint32_t gabs = 0;
+    {
+        uint32_t cnt = 0;
+        if (own_bin) for (uint32_t r = 0; r < (1u << rs); ++r) cnt += s_hist[1][(uint32_t)tid + r];
+        uint32_t incl = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t n = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += n; }
+        if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
+        __syncthreads();
+        uint32_t excl = incl - cnt;
+        for (int v = 0; v < (tid >> 6); ++v) excl += s_wave[v];
+        if (own_bin) {
+            gabs = (uint32_t)lo + excl;                                 // a batch holds < 2^32 records
+            gb[(uint64_t)b * nb + my_bin] = lo + excl;
+        }
+        if (b + 1 == lv.n_seg && tid == 0) gb[(uint64_t)lv.n_seg * nb] = hi;      // the closing offset = the number of records
+    }
+    if (hi == lo) return;                                               // (uniform)
+    // scatter pass: the rounds of k_lv_scatter_s<true>.  s_hist[1] still holds the counts: round 0 zeroes it behind its first barrier, and
+    // s_wave is next written behind that barrier too
+    uint32_t nxt[LV_ITEMS], nxt_aux[LV_ITEMS];
+    const uint64_t last = hi - 1, n_rounds = (hi - lo + LV_TILE - 1) / LV_TILE;
+    uint64_t pos = BACK ? lo + (n_rounds - 1) * LV_TILE : lo;
+#pragma unroll
+    for (int j = 0; j < LV_ITEMS; ++j) {
+        const uint64_t i = min(pos + (uint64_t)j * LV_THREADS + tid, last);
+        nxt[j] = recs32[i];
+        nxt_aux[j] = recs_aux[i];
+    }
+#pragma unroll
+    for (int j = 0; j < LV_ITEMS; ++j) { landed(nxt[j]); landed(nxt_aux[j]); }
+    uint32_t par = 0;
+    for (uint64_t r = 0; r < n_rounds; ++r, par ^= 1u) {
+        uint32_t* hist = s_hist[par];
+        uint64_t w[LV_ITEMS];
+#pragma unroll
+        for (int j = 0; j < LV_ITEMS; ++j) {
+            const uint64_t i = pos + (uint64_t)j * LV_THREADS + tid;
+            const uint32_t bn = i >= hi ? nb : narrow_bin(lv, b, nxt[j]);
+            w[j] = narrow_word(tight_rec(b >> lv.nr_shift, nxt[j], nxt_aux[j], s_rst[bn < nb ? bn : 0u]), 0u, bn);
+            if (bn != nb) atomicAdd(&hist[(bn << rs) | sub], 1u);
+        }
+        pos = BACK ? (r + 1 < n_rounds ? pos - LV_TILE : pos) : pos + LV_TILE;      // the next round (behind the last one: any loadable place)
+#pragma unroll
+        for (int j = 0; j < LV_ITEMS; ++j) {
+            const uint64_t i = min(pos + (uint64_t)j * LV_THREADS + tid, last);
+            nxt[j] = recs32[i];
+            nxt_aux[j] = recs_aux[i];
+        }
+        __syncthreads();
+        // exclusive scan of the counters: one per thread
+        const uint32_t cnt = (uint32_t)tid < n_ctr ? hist[tid] : 0u;
+        uint32_t incl = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t n = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += n; }
+        if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
+        s_hist[par ^ 1u][tid] = 0;                                      // the next round's counters
+        __syncthreads();
+        uint32_t excl = incl - cnt;
+        for (int v = 0; v < (tid >> 6); ++v) excl += s_wave[v];
+        s_loff[tid] = excl;
+        hist[tid] = excl;                                               // the counter's placement cursor
+        if (own_bin) s_grel[my_bin] = gabs - excl;                      // output index of staged record j of the bin = s_grel + j
+        __syncthreads();
+        if (own_bin) gabs += s_loff[(my_bin + 1) << rs] - excl;         // (the first counter of the discard bin holds the total)
+#pragma unroll
+        for (int j = 0; j < LV_ITEMS; ++j) {
+            const uint32_t bn = narrow_word_bin(w[j]);
+            if (bn != nb) s_buf[atomicAdd(&hist[(bn << rs) | sub], 1u)] = w[j];
+        }
+        __syncthreads();
+        const uint32_t total = s_loff[nb << rs];
+        uint64_t cv[LV_ITEMS];
+        uint32_t cg[LV_ITEMS];
+#pragma unroll
+        for (int it = 0; it < LV_ITEMS; ++it) cv[it] = s_buf[tid + it * LV_THREADS];
+#pragma unroll
+        for (int it = 0; it < LV_ITEMS; ++it) cg[it] = s_grel[(uint32_t)(tid + it * LV_THREADS) < total ? narrow_word_bin(cv[it]) : 0u] + (tid + it * LV_THREADS);   // (behind `total`: stale words)
+#pragma unroll
+        for (int j = 0; j < LV_ITEMS; ++j) { landed(nxt[j]); landed(nxt_aux[j]); }          // the wait for the prefetch in front of the stores
+#pragma unroll
+        for (int it = 0; it < LV_ITEMS; ++it)
+            if ((uint32_t)(tid + it * LV_THREADS) < total) out[cg[it]] = (uint32_t)cv[it];
+    }
+}
 __global__ void k_set2(unsigned long long* p, unsigned long long a, unsigned long long b) { p[0] = a; p[1] = b; }
 
 // multi-block exclusive scan helpers (chunks of SCAN_CHUNK elements per workgroup)

@@ -21,6 +21,7 @@
 #include "kq_device.h"
 #include "kq_partition.h"
 #include "kq_roff_host.h"
+#include "kq_seg_gate_host.h"
 
 using namespace kq;
 
@@ -649,7 +650,7 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
             h->map_passes = (int)value; return KQ_OK;
         }
         case KQ_OPT_KERNEL_SET:
-            if (value < 0 || (value & ~(int64_t)(7 | 16))) return fail(KQ_ERR_INVALID, "KQ_OPT_KERNEL_SET is a mask of bits 1, 2, 4, 16");
+            if (value < 0 || (value & ~(int64_t)(7 | 16 | 32 | 64))) return fail(KQ_ERR_INVALID, "KQ_OPT_KERNEL_SET is a mask of bits 1, 2, 4, 16, 32, 64");
             h->kernel_set = (int)value; return KQ_OK;
         case KQ_OPT_OVERLAP:
             if (value < 0 || value > 2) return fail(KQ_ERR_INVALID, "KQ_OPT_OVERLAP must be 0, 1 or 2");
@@ -726,6 +727,7 @@ struct PartPlan {
     int fmt;                  // record format between the stages (FMT_*)
     uint64_t n_max, R;
     uint32_t g1;              // P1 scatter workgroups
+    bool even_buckets = false;   // the slice's bucket offsets were read back and passed kq::seg_gate_even (count_partitioned)
     uint64_t m1_n, m2_n, sums_n, groups_n;
     // device pointers into h->work
     uint64_t *recs1, *recs2;
@@ -934,16 +936,20 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
 struct LevelIn { const uint64_t* recs; const uint8_t* aux; const unsigned long long *seg_lo, *seg_hi; uint32_t n_seg, spb; };
 // records grouped by the plan's own segment table p.seg_off[0..n_seg]: every segment ends where the next one starts
 static LevelIn own_segments(const PartPlan& p, const uint64_t* recs, const uint8_t* aux, uint32_t n_seg) { return LevelIn{recs, aux, p.seg_off, p.seg_off + 1, n_seg, 1}; }
+// rank replication of a level's bin counters: as many counters per bin as fit 512 (at most 64, one per lane)
+static LevelCfg with_rep_shift(const LevelCfg& lv) {
+    LevelCfg lvr = lv;
+    lvr.rep_shift = 0;
+    while (lvr.rep_shift < 6 && (((uint64_t)lv.nb + 1) << (lvr.rep_shift + 1)) <= 512) ++lvr.rep_shift;
+    return lvr;
+}
 // one generic split level: src -> out grouped by (segment, bin); afterwards gb[0..n_seg*nb] are the output offsets
 static void run_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const LevelIn& src, uint64_t* out, uint8_t* out_aux,
                       unsigned long long* gb = nullptr /*where the output offsets go (default p->group_base)*/) {
     if (!gb) gb = p->group_base;
     const uint64_t* in = src.recs; const uint8_t* in_aux = src.aux;
     const unsigned long long *seg_lo = src.seg_lo, *seg_hi = src.seg_hi;
-    LevelCfg lvr = lv;                                            // rank replication: as many counters per bin as fit 512 (at most 64, one per lane)
-    lvr.rep_shift = 0;
-    while (lvr.rep_shift < 6 && (((uint64_t)lv.nb + 1) << (lvr.rep_shift + 1)) <= 512) ++lvr.rep_shift;
-    const LevelCfg& lv_ = lvr;
+    const LevelCfg lv_ = with_rep_shift(lv);
     const int fmt = lv.narrow == 2 ? FMT_TOP8 : lv.narrow ? FMT_NARROW : in_aux != nullptr ? FMT_WIDE : FMT_PACK8;       // input format; lv.top8: packed in, narrow out
     const uint64_t groups = (uint64_t)(lv.n_seg / lv.spb) * lv.nb;
     hipLaunchKernelGGL(k_lv_units, dim3(1), dim3(1024), 0, h->stream, seg_lo, seg_hi, lv_, p->unit_base);
@@ -978,6 +984,15 @@ static void run_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const Level
     else if (fmt == FMT_WIDE) { if (small) KQ_LVS(FMT_WIDE, 512); else KQ_LVS(FMT_WIDE, NB_MAX); }
     else                      { if (small) KQ_LVS(FMT_PACK8, 512); else KQ_LVS(FMT_PACK8, NB_MAX); }
 #undef KQ_LVS
+    mark(h, "k_lv_scatter");
+}
+// The last level of a plan with a middle level, narrow records in and tight records out, fewer than 512 regions per segment: one
+// workgroup per segment counts, offsets and splits it (k_lv_segment_s).  Same output and same gb as run_level.
+static bool segment_level_ok(const PartPlan& p, const LevelCfg& lv) { return p.fmt == FMT_NARROW && lv.narrow == 1 && lv.rstart && lv.nr_shift != 0 && lv.nb < 512 && lv.spb == 1; }
+static void run_segment_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const uint64_t* in, const uint8_t* in_aux, uint64_t* out, unsigned long long* gb) {
+    mark(h, "segment_level");                                     // (zero-length: tells a reader of the stage list which form ran)
+    mark(h, "k_lv_hist+offsets+scan");                            // (no such stage here: the name stays so that stage_ms adds up)
+    hipLaunchKernelGGL(k_lv_segment_s, dim3(lv.n_seg), dim3(LV_THREADS), 0, h->stream, (const uint32_t*)in, in_aux, with_rep_shift(lv), p->seg_off, gb, (uint32_t*)out);
     mark(h, "k_lv_scatter");
 }
 static LevelCfg level_coarse_to_regions(const PartCfg& cfg) {
@@ -1245,7 +1260,12 @@ static P3Set sort_to_regions(kq_handle* h, PartPlan* p, const LevelIn& in, const
             uint8_t* m_aux = mid_to_2 ? p->a2() : p->a1();
             run_level(h, p, mid, in, m, m_aux);
             (void)hipMemcpyAsync(p->seg_off, p->group_base, (size_t)(((1u << NARROW_CBITS) << sb) + 1) * 8, hipMemcpyDeviceToDevice, h->stream);
-            run_level(h, p, last, own_segments(*p, m, m_aux, last.n_seg), fin, fin_aux, fin_base);
+            // KQ_OPT_KERNEL_SET: 64 = the segment kernel wherever it applies, 32 = never; else the slice's buckets decide (a hot
+            // sub-bucket keeps the unit path, which splits it over many workgroups)
+            if (segment_level_ok(*p, last) && ((h->kernel_set & 64) || (p->even_buckets && !(h->kernel_set & 32))))
+                run_segment_level(h, p, last, m, m_aux, fin, fin_base);
+            else
+                run_level(h, p, last, own_segments(*p, m, m_aux, last.n_seg), fin, fin_aux, fin_base);
         }
     } else if (p->two_level) {
         run_level(h, p, level_coarse_to_regions(p->cfg), in, fin, fin_aux, fin_base);
@@ -1291,9 +1311,16 @@ static int count_partitioned(kq_handle* h, const uint8_t* ab, uint64_t lead, uin
     mark(h, "start");
     run_p1(h, &p, p.cfg, ab, lead, len, er, p.recs1, p.a1(), AUX_IDX6, pinv);
     if (leveled && filtered) {
+        // (5-byte records with a middle level: the 257 bucket offsets come with the count, p.seg_off[256] = *p.total -- the
+        // last level's kernel depends on how even the buckets are, kq_seg_gate_host.h)
+        constexpr uint32_t NBK = 1u << NARROW_CBITS;
+        const bool with_offsets = p.fmt == FMT_NARROW && p.cfg.sub_bits != 0 && p.cfg.n_coarse == NBK;
+        unsigned long long offs[NBK + 1];
         unsigned long long n_recs = 0;
-        HIPC(hipMemcpyAsync(&n_recs, p.total, sizeof n_recs, hipMemcpyDeviceToHost, h->stream));
+        if (with_offsets) HIPC(hipMemcpyAsync(offs, p.seg_off, sizeof offs, hipMemcpyDeviceToHost, h->stream));
+        else HIPC(hipMemcpyAsync(&n_recs, p.total, sizeof n_recs, hipMemcpyDeviceToHost, h->stream));
         HIPC(hipStreamSynchronize(h->stream));
+        if (with_offsets) { n_recs = offs[NBK]; p.even_buckets = kq::seg_gate_even(offs, NBK); }
         rc = dest_take(h, p, std::min<uint64_t>(p.n_max, ((uint64_t)n_recs + 15) & ~7ull), &dst); if (rc) return rc;
     }
     return submit(h, sort_to_regions(h, &p, own_segments(p, p.recs1, p.a1(), p.cfg.n_coarse), dst), dst);

@@ -17,8 +17,8 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COUNT_KERNELS = ("k_p1_hist", "k_p1_scatter", "k_p1_scatter_s", "k_p1_offsets", "k_lv_units", "k_lv_hist", "k_lv_offsets", "k_lv_scatter", "k_lv_scatter_s", "k_count_regions",
-                 "k_count_regions_n32", "k_count_regions_q4", "k_scan_sums", "k_exclusive_scan", "k_scan_apply", "k_p3set", "k_set2", "k_count_direct")
+COUNT_KERNELS = ("k_p1_hist", "k_p1_scatter", "k_p1_scatter_s", "k_p1_offsets", "k_lv_units", "k_lv_hist", "k_lv_offsets", "k_lv_offsets_thread", "k_lv_scatter", "k_lv_scatter_s", "k_lv_segment_s",
+                 "k_count_regions", "k_count_regions_n32", "k_count_regions_q4", "k_p3_region_offsets", "k_count_regions_q4r", "k_fold_totals", "k_scan_sums", "k_exclusive_scan", "k_scan_apply", "k_p3set", "k_set2", "k_count_direct")
 
 
 def pmc(d):
@@ -49,7 +49,10 @@ def main():
            "hbm_bytes_per_kmer": (tf + tw) / steps / kmers_per_step,
            "what": f"configs[2] shape, {mbp} Mbp genome, 30x 150 bp reads in {steps} batches of {kmers_per_step} k-mers, k=21, counted in {ranges} map-range pass(es) (bench.py default workload)",
            "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `python3 bench.py --steps S --warmup 0 --no-cpu-baseline "
-                     "--no-extras`; all dispatches of the count kernels summed and divided by S; FETCH_SIZE x 2 (gfx950), WRITE_SIZE as is",
+                     "--no-extras`; all dispatches of the count kernels summed and divided by S; FETCH_SIZE x 2 (gfx950), WRITE_SIZE as is.  "
+                     "FETCH_SIZE appears to count requests that the Infinity Cache serves as well (MI355X_MICROARCH.md), so a re-read that hits there "
+                     "(k_lv_segment_s reading a segment it has just counted) still shows as fetched bytes: for such kernels the time, not this counter, "
+                     "is the evidence of what reached HBM",
            "kernels": rows, "hbm_read_bytes_per_step": round(tf / steps), "hbm_write_bytes_per_step": round(tw / steps),
            "hbm_bytes_per_launch": round((tf + tw) / steps), "algorithmic_bytes_per_step": 35 * kmers_per_step,
            "ratio_to_algorithmic": (tf + tw) / steps / (35 * kmers_per_step)}
