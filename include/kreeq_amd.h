@@ -163,7 +163,9 @@ void* kq_get_stream(kq_handle* h);
  *                          level through the unit path (k_lv_hist + offsets + scans + k_lv_scatter_s) also where the slice's even
  *                          buckets would select k_lv_segment_s (one workgroup per sub-bucket segment), 64 = k_lv_segment_s wherever
  *                          it applies, whatever the buckets look like and also in passes that do not read them back (tests,
- *                          measurement).  (8 is not assigned.)  Default 0. */
+ *                          measurement), 128 = the P1 scatter of narrow records behind a map-range filter with k_p1_scatter_s (every
+ *                          k-mer hashed and parked, the dropped ones too) instead of k_p1_scatter_c (survivors queued per wave ahead of
+ *                          the hash); bit 1 selects k_p1_scatter there too.  (8 is not assigned.)  Default 0. */
 enum { KQ_OPT_TRUST_CAPACITY = 1, KQ_OPT_COUNT_PATH = 2, KQ_OPT_SLICE_KMERS = 3, KQ_OPT_COUNT_MAP_RANGE = 4, KQ_OPT_PROFILE = 5,
        KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13, KQ_OPT_SHARD_WINDOW = 14,
        KQ_OPT_TEST_FAIL_PLAN = 100 /* failure-path tests only: the next partition plan of a count fails with KQ_ERR_NOMEM */ };

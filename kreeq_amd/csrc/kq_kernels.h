@@ -332,6 +332,145 @@ __global__ __launch_bounds__(TILE_THREADS * TPR, TOP8 ? 3 : 4 / TPR) void k_p1_s
     }
 }
 
+// inclusive prefix sum over the 64 lanes of a wave in registers: shifts by 1, 2, 4, 8 inside each row of 16 lanes, then the last lane
+// of row 0 / 2 to row 1 / 3 and the last lane of the lower half to the upper half (lanes without a source add 0)
+__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);      // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);      // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);      // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);      // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);      // row_bcast:15 into rows 1 and 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);      // row_bcast:31 into rows 2 and 3
+    return v;
+}
+// f(integral_constant N) for the smallest N of {4, 8, 9, 10, 16} with n <= N * per -- n is uniform, so one scalar branch picks a straight-line
+// body with static register indices; nothing for n == 0.  (At two map ranges a wave keeps 504 +- 16 of its 1008 starts, a round
+// 2016 +- 32 of 4032: N = 8 mostly, 9 otherwise.)
+template <class F>
+__device__ __forceinline__ void p1c_steps(uint32_t n, uint32_t per, F&& f) {
+    if (n == 0) return;
+    if (n <= 4 * per) f(std::integral_constant<int, 4>{});
+    else if (n <= 8 * per) f(std::integral_constant<int, 8>{});
+    else if (n <= 9 * per) f(std::integral_constant<int, 9>{});
+    else if (n <= 10 * per) f(std::integral_constant<int, 10>{});
+    else f(std::integral_constant<int, 16>{});
+}
+// The streamed scatter behind the map-range filter (BINMODE 4: narrow records, k <= 21), survivors compacted AHEAD of the hash.
+// The filter needs the canonical key alone, so the scan step of a start only decides it and appends a survivor -- key | idx6 << 42,
+// k <= 21: the key has at most 42 bits -- to a queue of its WAVE inside the stage: wave w owns s_buf[1024 w .. 1024 w + 1023] (a
+// wave has 64 x 16 starts per tile: the queue cannot overflow), the position is the wave's running count (wave-uniform) plus the
+// lane's rank among the step's survivors (ballot + mbcnt).  A dropped start costs nothing more.  Behind the scan the wave walks its
+// own queue 64 entries at a time: hash, bin count and record word for survivors only, every lane busy -- at two ranges 8 iterations
+// instead of 16 half-empty ones.  From the bin scan on the round is k_p1_scatter_s's (same barriers: the one between "every wave
+// has taken its queue into registers" and the placement is what lets queue and stage share their memory), with the placement and
+// the copy-out cut short at the wave's / the round's record count.  Same count matrix, cursors and output grouping as
+// k_p1_scatter_s<4, KC, 1>; the order inside one (workgroup, bucket) run is decided by atomics in both.
+template <int KC>
+__global__ __launch_bounds__(TILE_THREADS, 4) void k_p1_scatter_c(const uint8_t* __restrict__ ab, uint64_t lead, uint64_t len, int k_arg,
+                                                             PartCfg cfg, EmitRange er, const unsigned long long* __restrict__ m1,
+                                                             uint32_t* __restrict__ recs, uint8_t* __restrict__ recs_aux,
+                                                             const uint16_t* __restrict__ pinv /*packed input or null*/) {
+    constexpr uint32_t NB = 1u << NARROW_CBITS;
+    constexpr int THREADS = TILE_THREADS, QSHIFT = 2 * (int)NARROW_MAX_K, WQ = MS_TILE / (TILE_THREADS / 64);
+    static_assert(NB == TILE_THREADS && MS_TILE == TILE_THREADS * 16 && WQ == 64 * 16 && QSHIFT + 6 <= 64, "thread b owns bin b; a wave's queue holds its 1024 starts");
+    __shared__ uint32_t s_codes[TILE_THREADS];
+    __shared__ uint32_t s_inv[TILE_THREADS];
+    __shared__ uint64_t s_buf[MS_TILE];
+    __shared__ uint32_t s_hist[NB + 64], s_loff[NB + 1], s_grel[NB];
+    __shared__ __attribute__((aligned(16))) uint32_t s_wave[TILE_THREADS / 64];
+    // s_hist[NB + l]: what lane l adds for a word that is no record; never read
+    const int k = KC ? KC : k_arg;
+    __builtin_assume(k >= 1 && k <= (int)NARROW_MAX_K);                 // narrow records: table_hash is its Feistel branch, the dense phase has no other
+    const int tid = threadIdx.x;
+    uint64_t* const q = s_buf + (size_t)__builtin_amdgcn_readfirstlane(tid >> 6) * WQ;      // this wave's queue (the base in a scalar register)
+    const int64_t lo_valid = (int64_t)lead, hi_valid = (int64_t)(lead + len);
+    const uint64_t n_tiles = n_tiles_of(lead, len), stride = gridDim.x;
+    uint32_t gabs = (uint32_t)m1[(uint64_t)tid * gridDim.x * P1_F + (uint64_t)blockIdx.x * P1_F];      // bin tid's output cursor
+    s_hist[tid] = 0;
+    uint4 nxt = tile_fetch(ab, lo_valid, hi_valid, blockIdx.x, pinv);
+    landed(nxt.x); landed(nxt.y); landed(nxt.z); landed(nxt.w);
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += stride) {
+        uint32_t ct = (uint32_t)tid;                                    // the thread index, defined anew per round: the lane constants derived from it
+        asm volatile("" : "+v"(ct));                                    // (LDS addresses, offsets) are then not hoisted out of the tile loop, where they cost the registers the round needs
+        tile_store(nxt, lo_valid, hi_valid, tile, s_codes, s_inv, pinv != nullptr, (int)ct);        // barrier inside (covers the zeroed counters and the last copy-out's reads of the stage)
+        if (tile + stride < n_tiles) nxt = tile_fetch(ab, lo_valid, hi_valid, tile + stride, pinv, (int)ct);    // in flight during the split
+        uint32_t qn = 0;                                                // entries in the wave's queue (wave-uniform)
+        tile_lane_scan_all(s_codes, s_inv, lo_valid, tile, k, er, [&](int, bool valid, uint64_t fw, uint64_t rv, uint32_t prev, uint32_t next) {
+            const bool is_fw = fw < rv;
+            const uint64_t key = is_fw ? fw : rv;
+            const bool keep = valid && ((uint32_t)key & cfg.map_mask) - cfg.filt_lo < cfg.filt_hi - cfg.filt_lo;
+            const unsigned long long m = __ballot(keep);
+            if (keep) q[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = key | ((uint64_t)edge_idx6_any(is_fw, prev, next) << QSHIFT);
+            qn += (uint32_t)__popcll(m);
+        }, (int)ct);
+        // the wave reads what its own lanes wrote: LDS operations of a wave complete in order, the fence keeps the compiler from moving them
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        uint64_t w[16];
+        const uint32_t ql = ct & 63u;
+        const uint64_t* const qr = q + ql;
+#pragma unroll
+        for (int it = 0; it < 16; ++it) asm volatile("" : "=v"(w[it]));  // (no instruction: the words a short round leaves unset are not last round's, which would stay live through the scan)
+        p1c_steps(qn, 64u, [&](auto n_it) {
+            constexpr int N = decltype(n_it)::value;
+            uint64_t ahead = qr[0];                                     // (reads stay inside the wave's queue whatever qn is; behind qn: stale, binned NB)
+#pragma unroll
+            for (int it = 0; it < N; ++it) {
+                const uint64_t qw = ahead;
+                if (it + 1 < N) ahead = qr[(it + 1) * 64];              // one entry ahead of the hash
+                const uint64_t h = table_hash(qw & ((1ull << QSHIFT) - 1), (uint32_t)k);
+                const uint32_t b = ql + (uint32_t)it * 64u < qn ? (uint32_t)(h >> (64 - NARROW_CBITS)) : NB + ql;
+                atomicAdd(&s_hist[b], 1u);                              // (behind the queue's end: the lane's own spare counter -- no branch, no address shared)
+                w[it] = narrow_word(narrow_main(h), narrow_aux(h, (uint32_t)(qw >> QSHIFT)), b);
+                __builtin_amdgcn_sched_barrier(0);                      // one hash at a time: interleaved, their temporaries spill
+            }
+        });
+        __syncthreads();
+        // exclusive scan of the 256 counts: one bin per thread
+        const uint32_t cnt = s_hist[ct];
+        const uint32_t incl = wave_incl_scan_dpp(cnt);                  // (six data-parallel adds: no LDS round trip per step, the round waits on this chain)
+        if (ql == 63) s_wave[ct >> 6] = incl;
+        __syncthreads();                                                // (also: every wave holds its queue in registers -- the stage may be overwritten)
+        {
+            const uint4 wt = *reinterpret_cast<const uint4*>(s_wave);  // the four wave totals in one read
+            const uint32_t wv = ct >> 6;
+            const uint32_t excl = incl - cnt + (wv > 0 ? wt.x : 0u) + (wv > 1 ? wt.y : 0u) + (wv > 2 ? wt.z : 0u);
+            s_loff[ct] = excl;
+            if (ct == NB - 1) s_loff[NB] = excl + cnt;
+            s_hist[ct] = excl;                                          // the bin's placement cursor
+            s_grel[ct] = gabs - excl;                                   // output index of staged record j of bin tid = s_grel + j
+            gabs += cnt;
+        }
+        __syncthreads();
+        p1c_steps(qn, 64u, [&](auto n_it) {
+            constexpr int N = decltype(n_it)::value;
+            uint32_t pl[N];                                             // (two loops: the cursor atomics are in flight together)
+#pragma unroll
+            for (int it = 0; it < N; ++it) pl[it] = atomicAdd(&s_hist[narrow_word_bin(w[it])], 1u);
+#pragma unroll
+            for (int it = 0; it < N; ++it) if (narrow_word_bin(w[it]) < NB) s_buf[pl[it]] = w[it];
+        });
+        __syncthreads();
+        const uint32_t total = __builtin_amdgcn_readfirstlane(s_loff[NB]);          // <= TILE_STARTS; scalar: the copy-out's length hangs on it
+        s_hist[ct] = 0;                                                 // (all placements are behind the barrier above)
+        p1c_steps(total, (uint32_t)THREADS, [&](auto n_it) {
+            constexpr int N = decltype(n_it)::value;
+            uint64_t cv[N];
+            uint32_t cg[N];
+#pragma unroll
+            for (int it = 0; it < N; ++it) cv[it] = s_buf[ct + it * THREADS];
+#pragma unroll
+            for (int it = 0; it < N; ++it) cg[it] = s_grel[ct + it * THREADS < total ? narrow_word_bin(cv[it]) : 0u] + (ct + it * THREADS);   // (behind `total` the stage holds stale words)
+            landed(nxt.x); landed(nxt.y); landed(nxt.z); landed(nxt.w); // the wait for the prefetch in front of the stores (block_multisplit)
+#pragma unroll
+            for (int it = 0; it < N; ++it) {
+                if (ct + it * THREADS < total) { recs[cg[it]] = (uint32_t)cv[it]; recs_aux[cg[it]] = (uint8_t)(cv[it] >> 48); }
+            }
+        });
+        landed(nxt.x); landed(nxt.y); landed(nxt.z); landed(nxt.w);     // (a round without records)
+    }
+}
+
 // ---- one generic level of the record split (LevelCfg) -----------------------------------------
 // work units: segment b is cut into ceil(size_b / P2_UNIT) units; unit_base = exclusive prefix
 // (one workgroup; n_seg <= SEG_MAX: every thread takes a run of consecutive segments, the run totals are scanned)

@@ -650,7 +650,7 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
             h->map_passes = (int)value; return KQ_OK;
         }
         case KQ_OPT_KERNEL_SET:
-            if (value < 0 || (value & ~(int64_t)(7 | 16 | 32 | 64))) return fail(KQ_ERR_INVALID, "KQ_OPT_KERNEL_SET is a mask of bits 1, 2, 4, 16, 32, 64");
+            if (value < 0 || (value & ~(int64_t)(7 | 16 | 32 | 64 | 128))) return fail(KQ_ERR_INVALID, "KQ_OPT_KERNEL_SET is a mask of bits 1, 2, 4, 16, 32, 64, 128");
             h->kernel_set = (int)value; return KQ_OK;
         case KQ_OPT_OVERLAP:
             if (value < 0 || value > 2) return fail(KQ_ERR_INVALID, "KQ_OPT_OVERLAP must be 0, 1 or 2");
@@ -918,7 +918,10 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     // narrow records: the streamed scatter (k_p1_scatter_s); a pass that keeps every k-mer splits two tiles per round, a filtered one one
 #define KQ_P1N(B, K, T) do { if (h->kernel_set & 1) KQ_P1S(FMT_NARROW, 512, B, K); else \
         hipLaunchKernelGGL((k_p1_scatter_s<B, K, T>), dim3(p->g1), dim3(TILE_THREADS * T), 0, h->stream, ab, lead, len, h->k, cfg, er, p->m1, (uint32_t*)out, out_aux, pinv); } while (0)
-    else if (narrow_filt)  { if (h->k == 21) KQ_P1N(4, 21, 1); else KQ_P1N(4, 0, 1); }
+    // behind the map-range filter: survivors compacted ahead of the hash (k_p1_scatter_c); kernel_set bit 128 = the previous kernel
+#define KQ_P1C(K) do { if (h->kernel_set & (1 | 128)) KQ_P1N(4, K, 1); else \
+        hipLaunchKernelGGL((k_p1_scatter_c<K>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, cfg, er, p->m1, (uint32_t*)out, out_aux, pinv); } while (0)
+    else if (narrow_filt)  { if (h->k == 21) KQ_P1C(21); else KQ_P1C(0); }
     else if (narrow_win)   { if (h->k == 21) KQ_P1N(6, 21, 1); else KQ_P1N(6, 0, 1); }
     else if (cfg.narrow)   { if (plain && h->k == 21) KQ_P1N(2, 21, KQ_P1S_TPR); else if (plain) KQ_P1N(2, 0, KQ_P1S_TPR); else KQ_P1N(0, 0, 1); }     // 256 buckets
     else if (out_aux && plain && h->k == 31) { if (small) KQ_P1S(FMT_WIDE, 512, 1, 31); else KQ_P1S(FMT_WIDE, NB_MAX, 1, 31); }   // the HiFi k
@@ -928,6 +931,7 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     else              { if (small) KQ_P1S(FMT_PACK8, 512, 0, 0); else KQ_P1S(FMT_PACK8, NB_MAX, 0, 0); }
 #undef KQ_P1S
 #undef KQ_P1N
+#undef KQ_P1C
 #undef KQ_P1T
     mark(h, "k_p1_scatter");
 }
