@@ -166,8 +166,10 @@ void* kq_get_stream(kq_handle* h);
  *                          measurement), 128 = the P1 scatter of narrow records behind a map-range filter with k_p1_scatter_s (every
  *                          k-mer hashed and parked, the dropped ones too) instead of k_p1_scatter_c (survivors queued per wave ahead of
  *                          the hash); bit 1 selects k_p1_scatter there too.  (8 is not assigned.)  Default 0. */
+/*   KQ_OPT_SUBGRAPH_BATCH  (on the DATABASE handle) searches per batch of kq_subgraph_best_first; 0 (default) = automatic: a scratch arena of
+ *                          1 GiB divided by the bytes of one search's state block at the call's depth.  Results never depend on it. */
 enum { KQ_OPT_TRUST_CAPACITY = 1, KQ_OPT_COUNT_PATH = 2, KQ_OPT_SLICE_KMERS = 3, KQ_OPT_COUNT_MAP_RANGE = 4, KQ_OPT_PROFILE = 5,
-       KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13, KQ_OPT_SHARD_WINDOW = 14,
+       KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13, KQ_OPT_SHARD_WINDOW = 14, KQ_OPT_SUBGRAPH_BATCH = 15,
        KQ_OPT_TEST_FAIL_PLAN = 100 /* failure-path tests only: the next partition plan of a count fails with KQ_ERR_NOMEM */ };
 int  kq_set_option(kq_handle* h, int option, int64_t value);
 int  kq_get_profile(kq_handle* h, char* buf, uint64_t cap);
@@ -418,12 +420,21 @@ int  kq_import_map_image(kq_handle* h, uint16_t map, const void* image, uint64_t
  *     its database entry, after the last round.  The frontier stays on the device; its size returns to the host once per
  *     round, and an empty one ends the rounds.  *n_added = k-mers inserted.  KQ_ERR_TABLE_FULL when the frontier list, the
  *     visited set or `sub` cannot grow.
+ * kq_subgraph_best_first  Replaces DBG::bestFirst / dijkstra (:417-579) for one resident map range: one search per k-mer of `sub`, at
+ *     most depth + 1 pops each, all of a batch in ONE kernel launch with one search per lane (kq_bestfirst_core.h: a bounded
+ *     state block of 9 + 4 depth nodes per search, KQ_OPT_SUBGRAPH_BATCH searches per batch).  Membership is tested against the
+ *     seed set only; an edge counter > cov_cutoff is followed when its neighbour is in `db`; the source's counters are those of
+ *     its `sub` entry, every other k-mer's its logical `db` entry.  The k-mers on the paths back from every destination are
+ *     inserted, with their database entries, after the last batch.  Only a batch's total returns to the host.  *n_added =
+ *     k-mers inserted; the result does not depend on the batch size or the launch geometry.  KQ_ERR_TABLE_FULL when the found
+ *     list, the visited set or `sub` cannot grow; KQ_ERR_NOMEM when the state blocks of a batch cannot be allocated.
  * kq_subgraph_trim        Replaces DBG::removeMissingEdges (:599-625): every edge counter > cov_cutoff of `sub` whose neighbour
  *     k-mer is not in `sub` becomes 0, in both tiers; counters <= cov_cutoff are not examined.  Not to be mixed with inserts. */
 enum { KQ_SUBGRAPH_NO_REFERENCE = 1 };
 int  kq_subgraph_seed(kq_handle* db, kq_handle* sub, const char* bases, uint64_t len, uint32_t flags);
 int  kq_subgraph_seed_dev(kq_handle* db, kq_handle* sub, const char* d_bases, uint64_t len, uint32_t flags);
 int  kq_subgraph_expand(kq_handle* db, kq_handle* sub, int depth, uint64_t* n_added);
+int  kq_subgraph_best_first(kq_handle* db, kq_handle* sub, int depth, uint32_t cov_cutoff, uint64_t* n_added);
 int  kq_subgraph_trim(kq_handle* sub, uint32_t cov_cutoff);
 
 #ifdef __cplusplus

@@ -17,7 +17,7 @@ SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profi
            "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
            "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_lookup_keys", "kq_branch_scan", "kq_merge", "kq_import", "kq_export",
-           "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_trim"]
+           "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_best_first", "kq_subgraph_trim"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
 SUBGRAPH_NO_REFERENCE = 1                # KQ_SUBGRAPH_NO_REFERENCE
@@ -135,6 +135,7 @@ def load():
     L.kq_subgraph_seed.argtypes = [vp, vp, vp, u64, u32]
     L.kq_subgraph_seed_dev.argtypes = [vp, vp, vp, u64, u32]
     L.kq_subgraph_expand.argtypes = [vp, vp, ci, C.POINTER(u64)]
+    L.kq_subgraph_best_first.argtypes = [vp, vp, ci, u32, C.POINTER(u64)]
     L.kq_subgraph_trim.argtypes = [vp, u32]
     _lib = L
     return L
@@ -203,7 +204,7 @@ class KreeqDB:
         """option: 'trust_capacity' | 'count_path' ('auto'|'direct'|'partitioned') | 'slice_kmers' | 'count_map_range' ((lo, hi)) |
         'kernel_set' (measurement only: mask of bits 1, 2, 4, 16, 32, 64, 128 -- KQ_OPT_KERNEL_SET in include/kreeq_amd.h; 32 / 64 = the last
         split level never / wherever possible with one workgroup per segment; 128 = the previous P1 scatter behind a map-range filter) | ..."""
-        opt = {"trust_capacity": 1, "count_path": 2, "slice_kmers": 3, "count_map_range": 4, "profile": 5, "lookup_path": 6, "merge_path": 7, "narrow_mid": 8, "pending_bytes": 9, "bucket_window": 10, "overlap": 11, "count_map_passes": 12, "kernel_set": 13, "shard_window": 14, "test_fail_plan": 100}[option]
+        opt = {"trust_capacity": 1, "count_path": 2, "slice_kmers": 3, "count_map_range": 4, "profile": 5, "lookup_path": 6, "merge_path": 7, "narrow_mid": 8, "pending_bytes": 9, "bucket_window": 10, "overlap": 11, "count_map_passes": 12, "kernel_set": 13, "shard_window": 14, "subgraph_batch": 15, "test_fail_plan": 100}[option]
         if option == "count_map_range":
             value = int(value[0]) | (int(value[1]) << 16)
         if option in ("count_path", "lookup_path", "merge_path"):
@@ -427,6 +428,13 @@ class KreeqDB:
         """`depth` rounds of the traversal from the k-mers of `sub` through this database; -> k-mers added"""
         n = C.c_uint64(0)
         _check(load().kq_subgraph_expand(self._h, sub._h, depth, C.byref(n)))
+        return n.value
+
+    def subgraph_best_first(self, sub, depth, cov_cutoff=0):
+        """one best-first search of at most depth + 1 pops per k-mer of `sub` through this database, every search on the GPU
+        (set_option('subgraph_batch', n) on this handle fixes the searches per batch); -> k-mers added"""
+        n = C.c_uint64(0)
+        _check(load().kq_subgraph_best_first(self._h, sub._h, depth, cov_cutoff, C.byref(n)))
         return n.value
 
     def subgraph_trim(self, cov_cutoff=0):

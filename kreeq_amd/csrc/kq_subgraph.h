@@ -1,10 +1,12 @@
 // kq_subgraph.h -- kernels of the subgraph mode (reference src/subgraph.cpp): seed a second table from the k-mers of a set
-// of sequences, expand it level by level along the edge counters of the database, clear the edges that lead outside it.
-// gfx950 only.  Host side: kq_subgraph_seed(_dev) / kq_subgraph_expand / kq_subgraph_trim in kreeq_amd.hip.
+// of sequences, expand it level by level along the edge counters of the database or by one best-first search per seed, clear
+// the edges that lead outside it.
+// gfx950 only.  Host side: kq_subgraph_seed(_dev) / kq_subgraph_expand / kq_subgraph_best_first / kq_subgraph_trim in kreeq_amd.hip.
 //
 // Every probe here is one random 64-byte sector read of a table region (table_find), as in k_lookup; nothing in this
 // file is bound by anything else, so the kernels keep the one-item-per-thread form at full occupancy.
 #pragma once
+#include "kq_bestfirst_core.h"
 
 namespace kq {
 
@@ -116,6 +118,46 @@ __global__ __launch_bounds__(256) void k_sg_seed_add(TableView db, TableView sub
 // been found before (claim in `visited`, an open-addressing key set: the reference finds a k-mer again in later rounds,
 // the union over the rounds is the same).  The winners of a wave reserve their output range with one atomic.
 struct SgExpandState { unsigned long long n_ents, n_instances; unsigned int err, pad; };
+// claims `key` in the visited set (open addressing, EMPTY_KEY = free): true for the one work item that found it first
+__device__ __forceinline__ bool sg_claim(uint64_t* __restrict__ visited, uint64_t visited_mask, uint64_t key, SgExpandState* __restrict__ st) {
+    uint64_t j = mix64(key ^ 0x9E3779B97F4A7C15ull) & visited_mask;
+    for (uint64_t probe = 0; probe <= visited_mask; ++probe, j = (j + 1) & visited_mask) {
+        uint64_t cur = ld_relaxed(&visited[j]);
+        if (cur == EMPTY_KEY) {
+            cur = atomicCAS((unsigned long long*)&visited[j], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
+            if (cur == EMPTY_KEY) return true;
+        }
+        if (cur == key) return false;
+    }
+    atomicOr(&st->err, 1u);
+    return false;
+}
+// the logical entry of the database slot `s` of `key` (hash h), as kq_export writes it
+__device__ __forceinline__ kq_entry sg_entry_of(const TableView& db, uint64_t key, uint64_t h, const Slot* s) {
+    const Logical L = logical_of(db, h, s->w0, s->e8);
+    kq_entry e;
+    e.key = key;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { e.fw[w] = L.e[w]; e.bw[w] = L.e[4 + w]; }
+    e.cov = L.cov;
+    e.hc = L.cov > LOW_TIER_MAX;
+    return e;
+}
+// appends the entries of the winners of a wave to the found list: one atomic per wave reserves their range.  Every lane of
+// the wave calls this.
+__device__ __forceinline__ void sg_append(bool win, const kq_entry& found, kq_entry* ents, uint64_t ents_cap, SgExpandState* __restrict__ st) {
+    const uint64_t mask = __ballot(win);
+    if (!mask) return;
+    const uint32_t lane = __lane_id();
+    const uint32_t leader = (uint32_t)__ffsll((unsigned long long)mask) - 1u;
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(&st->n_ents, (unsigned long long)__popcll(mask));
+    base = __shfl(base, (int)leader, 64);
+    if (win) {
+        const uint64_t o = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        if (o < ents_cap) ents[o] = found; else atomicOr(&st->err, 2u);
+    }
+}
 __global__ __launch_bounds__(256) void k_sg_expand(TableView db, TableView sub, kq_entry* ents, uint64_t f_lo, uint64_t f_hi,
                                                     uint64_t ents_cap, uint64_t* __restrict__ visited, uint64_t visited_mask,
                                                     SgExpandState* __restrict__ st) {
@@ -136,42 +178,13 @@ __global__ __launch_bounds__(256) void k_sg_expand(TableView db, TableView sub, 
                 if (!table_find(sub, h)) {
                     const Slot* s = table_find(db, h);
                     if (s) {
-                        uint64_t j = mix64(key ^ 0x9E3779B97F4A7C15ull) & visited_mask;
-                        bool placed = false;
-                        for (uint64_t probe = 0; probe <= visited_mask; ++probe, j = (j + 1) & visited_mask) {
-                            uint64_t cur = ld_relaxed(&visited[j]);
-                            if (cur == EMPTY_KEY) {
-                                cur = atomicCAS((unsigned long long*)&visited[j], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-                                if (cur == EMPTY_KEY) { win = true; placed = true; break; }
-                            }
-                            if (cur == key) { placed = true; break; }
-                        }
-                        if (!placed) atomicOr(&st->err, 1u);
-                        if (win) {
-                            const Logical L = logical_of(db, h, s->w0, s->e8);
-                            found.key = key;
-#pragma unroll
-                            for (int w = 0; w < 4; ++w) { found.fw[w] = L.e[w]; found.bw[w] = L.e[4 + w]; }
-                            found.cov = L.cov;
-                            found.hc = L.cov > LOW_TIER_MAX;
-                            n_inst += L.cov;
-                        }
+                        win = sg_claim(visited, visited_mask, key, st);
+                        if (win) { found = sg_entry_of(db, key, h, s); n_inst += found.cov; }
                     }
                 }
             }
         }
-        const uint64_t mask = __ballot(win);
-        if (mask) {
-            const uint32_t lane = __lane_id();
-            const uint32_t leader = (uint32_t)__ffsll((unsigned long long)mask) - 1u;
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(&st->n_ents, (unsigned long long)__popcll(mask));
-            base = __shfl(base, (int)leader, 64);
-            if (win) {
-                const uint64_t o = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-                if (o < ents_cap) ents[o] = found; else atomicOr(&st->err, 2u);
-            }
-        }
+        sg_append(win, found, ents, ents_cap, st);
     }
     const uint64_t a = block_sum(n_inst);
     if (threadIdx.x == 0 && a) atomicAdd(&st->n_instances, (unsigned long long)a);
@@ -187,6 +200,94 @@ __global__ __launch_bounds__(256) void k_sg_visited_fill(const kq_entry* __restr
             placed = atomicCAS((unsigned long long*)&visited[j], (unsigned long long)EMPTY_KEY, (unsigned long long)key) == EMPTY_KEY;
         if (!placed) atomicOr(&st->err, 1u);
     }
+}
+
+// ---- best-first (DBG::bestFirst / dijkstra, src/subgraph.cpp:417-579) ----------------------------------------------------
+// One search per seed k-mer and per LANE: the search is serial within one source and independent between sources (read-only
+// database, read-only seed set), and its state is bounded (kq_bestfirst_core.h), so each lane runs the whole search -- at
+// most depth + 1 pops -- on a state block of its own in a global arena, with no host round trip.  Every heap step is a
+// dependent access to that block; occupancy is what hides it.
+//
+// the two questions of the search core, answered by table probes; counters are the LOGICAL ones (the high-copy tier's for a
+// high-copy k-mer), membership is against `sub`, which holds the seeds and nothing else until the last batch is over (:453)
+struct SgBfGraph {
+    const TableView& db;
+    const TableView& sub;
+    uint32_t cov_cutoff;
+    __device__ bool is_seed(uint64_t key) const { return table_find(sub, table_hash(key, sub.k)) != nullptr; }
+    __device__ int db_mask(uint64_t key) const {
+        const uint64_t h = table_hash(key, db.k);
+        const Slot* s = table_find(db, h);
+        if (!s) return -1;
+        const Logical L = logical_of(db, h, s->w0, s->e8);
+        int m = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) m |= (int)(L.e[e] > cov_cutoff) << e;
+        return m;
+    }
+};
+struct SgBfState { unsigned long long n_found; unsigned int err, pad; };      // of one batch: discovered nodes (with repeats), OR of the error codes
+// seeds[i] (i < n): the source of search i with its merged subgraph entry (:470), as k_export lists it; arena + i * block_bytes:
+// its state block, whose index the host has filled with 0xFF.  The flagged nodes stay in the block for k_sg_bf_collect.
+__global__ __launch_bounds__(256) void k_sg_bf_search(TableView db, TableView sub, const kq_entry* __restrict__ seeds, uint64_t n, int depth,
+                                                       uint32_t cov_cutoff, uint8_t* __restrict__ arena, uint64_t block_bytes, SgBfState* __restrict__ st) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, n_iter = (n + stride - 1) / stride;      // whole waves stay in the loop
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t it = 0; it < n_iter; ++it, i += stride) {
+        uint32_t found = 0, err = 0;
+        if (i < n) {
+            const kq_entry src = seeds[i];
+            uint32_t mask = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) mask |= (uint32_t)(src.fw[e] > cov_cutoff) << e | (uint32_t)(src.bw[e] > cov_cutoff) << (4 + e);
+            void* block = arena + i * block_bytes;
+            const SgBfGraph g{db, sub, cov_cutoff};
+            found = kqbf::search(block, depth, (int)db.k, src.key, mask, g);
+            err = kqbf::head_of(block)->err;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { found += __shfl_xor(found, o, 64); err |= __shfl_xor(err, o, 64); }
+        if (__lane_id() == 0) {
+            if (found) atomicAdd(&st->n_found, (unsigned long long)found);
+            if (err) atomicOr(&st->err, err);
+        }
+    }
+}
+// One work item per (search, node slot) of the batch: a flagged node claims its key in the visited set, so that a k-mer that
+// many searches discovered is listed once, and the winner appends the k-mer's database entry to the found list.
+__global__ __launch_bounds__(256) void k_sg_bf_collect(TableView db, const uint8_t* __restrict__ arena, uint64_t block_bytes, uint64_t n, uint32_t n_slots,
+                                                        kq_entry* ents, uint64_t ents_cap, uint64_t* __restrict__ visited, uint64_t visited_mask,
+                                                        SgExpandState* __restrict__ st) {
+    const uint64_t n_items = n * n_slots;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, n_iter = (n_items + stride - 1) / stride;
+    uint64_t n_inst = 0;
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t it = 0; it < n_iter; ++it, i += stride) {
+        bool win = false;
+        kq_entry found;
+        if (i < n_items) {
+            const uint64_t search = i / n_slots;
+            const uint32_t slot = (uint32_t)(i - search * n_slots);
+            const uint8_t* block = arena + search * block_bytes;
+            const kqbf::Head* hd = (const kqbf::Head*)block;
+            if (slot < hd->n_nodes && hd->n_nodes <= n_slots) {
+                const kqbf::Node* node = (const kqbf::Node*)(block + sizeof(kqbf::Head)) + slot;
+                if (node->flags & kqbf::F_FOUND) {
+                    const uint64_t key = node->key;
+                    const uint64_t h = table_hash(key, db.k);
+                    const Slot* s = table_find(db, h);                   // present: the search met the key in the database
+                    if (!s) atomicOr(&st->err, 4u);
+                    else {
+                        win = sg_claim(visited, visited_mask, key, st);
+                        if (win) { found = sg_entry_of(db, key, h, s); n_inst += found.cov; }
+                    }
+                }
+            }
+        }
+        sg_append(win, found, ents, ents_cap, st);
+    }
+    const uint64_t a = block_sum(n_inst);
+    if (threadIdx.x == 0 && a) atomicAdd(&st->n_instances, (unsigned long long)a);
 }
 
 // ---- trim (DBG::removeMissingEdges, src/subgraph.cpp:599-625) -----------------------------------------------------------

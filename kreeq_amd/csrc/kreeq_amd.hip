@@ -209,6 +209,7 @@ struct kq_handle {
                                          // changes its content: the address-keyed KQ_OPT_COUNT_MAP_PASSES cache must not see it
     bool test_fail_plan = false;         // KQ_OPT_TEST_FAIL_PLAN: the next partition plan fails with KQ_ERR_NOMEM (failure-path tests)
     DevBuf hot;                          // k_count_regions' list of skewed regions
+    uint64_t sg_batch = 0;               // KQ_OPT_SUBGRAPH_BATCH: searches per batch of kq_subgraph_best_first, 0 = from the scratch budget
 
     TableView view() const {
         TableView v; v.slots = slots - (reg_lo() << REGION_SHIFT); v.n_regions = n_regions; v.hc = hc; v.hc_mask = hc_cap - 1; v.st = st; v.k = (uint32_t)k;
@@ -671,6 +672,9 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
         case KQ_OPT_SLICE_KMERS:
             if (value < 1) return fail(KQ_ERR_INVALID, "KQ_OPT_SLICE_KMERS must be positive");
             h->slice_kmers = (uint64_t)value; h->slice_user = true; return KQ_OK;
+        case KQ_OPT_SUBGRAPH_BATCH:
+            if (value < 0) return fail(KQ_ERR_INVALID, "KQ_OPT_SUBGRAPH_BATCH must be 0 (automatic) or a number of searches");
+            h->sg_batch = (uint64_t)value; return KQ_OK;
         default: return fail(KQ_ERR_INVALID, "unknown option %d", option);
     }
 }
@@ -2574,27 +2578,18 @@ int kq_subgraph_seed(kq_handle* db, kq_handle* sub, const char* bases, uint64_t 
     return kq_subgraph_seed_dev(db, sub, (const char*)d, len, flags);
 }
 
-int kq_subgraph_expand(kq_handle* db, kq_handle* sub, int depth, uint64_t* n_added) {
-    int rc = sg_check(db, sub);
-    if (rc) return rc;
-    if (!n_added) return fail(KQ_ERR_INVALID, "null n_added");
-    if (depth < 0 || depth > 255) return fail(KQ_ERR_INVALID, "search depth %d outside 0..255", depth);      // uint8_t in the reference (src/subgraph.cpp:307)
-    *n_added = 0;
-    rc = sg_begin(db, sub);
-    if (rc) return rc;
-    rc = check_errors(sub);
-    if (rc) return rc;
-    const uint64_t n_seed = sub->st_host->slots_used;
-    if (!depth || !n_seed) return KQ_OK;
-    hipStream_t st = sub->stream;
+}  // extern "C"
+namespace {
+// The found list of an expansion -- ents[0, n_seed) = the seed k-mers with their subgraph entries, ents[n_seed, n_ents) = what
+// was found, in the order found -- and the visited key set (load <= 1/2) of the k-mers found.  Both double like a table.
+struct SgFound {
     DevPtrs mem;
-    SgExpandState state{};
     SgExpandState* d_state = nullptr;
     kq_entry* d_ents = nullptr; uint64_t* d_vis = nullptr;
     uint64_t ents_cap = 0, vis_size = 0;
-    // room for a round that finds 8 k-mers per frontier k-mer: the found list and the visited set (load <= 1/2) double like a table
-    auto make_room = [&](uint64_t n_ents, uint64_t frontier) -> int {
-        const uint64_t need = n_ents + 8 * frontier;
+    // room for `need` entries in all, n_ents of which are there
+    int room(kq_handle* sub, uint64_t n_seed, uint64_t n_ents, uint64_t need) {
+        hipStream_t st = sub->stream;
         if (need > ents_cap) {
             uint64_t cap = std::max<uint64_t>(ents_cap, 1024);
             while (cap < need) cap *= 2;
@@ -2616,7 +2611,32 @@ int kq_subgraph_expand(kq_handle* db, kq_handle* sub, int depth, uint64_t* n_add
             if (n_ents > n_seed) hipLaunchKernelGGL(k_sg_visited_fill, dim3(grid_for(sub, n_ents - n_seed, 256)), dim3(256), 0, st, d_ents, n_seed, n_ents, d_vis, size - 1, d_state);
         }
         return KQ_OK;
-    };
+    }
+};
+}  // namespace
+extern "C" {
+
+int kq_subgraph_expand(kq_handle* db, kq_handle* sub, int depth, uint64_t* n_added) {
+    int rc = sg_check(db, sub);
+    if (rc) return rc;
+    if (!n_added) return fail(KQ_ERR_INVALID, "null n_added");
+    if (depth < 0 || depth > 255) return fail(KQ_ERR_INVALID, "search depth %d outside 0..255", depth);      // uint8_t in the reference (src/subgraph.cpp:307)
+    *n_added = 0;
+    rc = sg_begin(db, sub);
+    if (rc) return rc;
+    rc = check_errors(sub);
+    if (rc) return rc;
+    const uint64_t n_seed = sub->st_host->slots_used;
+    if (!depth || !n_seed) return KQ_OK;
+    hipStream_t st = sub->stream;
+    SgFound fl;
+    DevPtrs& mem = fl.mem;
+    SgExpandState state{};
+    SgExpandState*& d_state = fl.d_state;
+    kq_entry*& d_ents = fl.d_ents; uint64_t*& d_vis = fl.d_vis;
+    uint64_t &ents_cap = fl.ents_cap, &vis_size = fl.vis_size;
+    // room for a round that finds 8 k-mers per frontier k-mer
+    auto make_room = [&](uint64_t n_ents, uint64_t frontier) -> int { return fl.room(sub, n_seed, n_ents, n_ents + 8 * frontier); };
     if (mem.alloc((void**)&d_state, sizeof(SgExpandState)) != hipSuccess) return fail(KQ_ERR_NOMEM, "no device memory");
     rc = make_room(n_seed, n_seed);
     if (rc) return rc;
@@ -2644,6 +2664,82 @@ int kq_subgraph_expand(kq_handle* db, kq_handle* sub, int depth, uint64_t* n_add
         rc = reserve(sub, n_found, state.n_instances);
         if (rc) return rc;
         hipLaunchKernelGGL(k_import, dim3(grid_for(sub, n_found, 256)), dim3(256), 0, st, sub->view(), (const kq_entry*)(d_ents + n_seed), n_found);
+        HIPC(hipGetLastError());
+        rc = kq_sync(sub);
+        if (rc) return rc;
+    }
+    *n_added = n_found;
+    return KQ_OK;
+}
+
+// Scratch budget of the best-first searches: every search of a batch owns one state block of kqbf::block_bytes(depth) bytes
+// (2.8 KB at depth 21, 33 KB at depth 255), so a batch is SG_BF_ARENA_BYTES / block bytes searches (at least one, at most the
+// seeds there are): 380 000 at depth 21, 32 000 at depth 255 -- either fills the chip's 2^19 lanes most of the way, and 1 GiB is
+// small next to a database that is worth a device search.  KQ_OPT_SUBGRAPH_BATCH fixes the number instead (tests).
+constexpr uint64_t SG_BF_ARENA_BYTES = 1ull << 30;
+
+int kq_subgraph_best_first(kq_handle* db, kq_handle* sub, int depth, uint32_t cov_cutoff, uint64_t* n_added) {
+    int rc = sg_check(db, sub);
+    if (rc) return rc;
+    if (!n_added) return fail(KQ_ERR_INVALID, "null n_added");
+    if (depth < 0 || depth > kqbf::MAX_DEPTH) return fail(KQ_ERR_INVALID, "search depth %d outside 0..255", depth);      // uint8_t in the reference (src/subgraph.cpp:460)
+    *n_added = 0;
+    rc = sg_begin(db, sub);
+    if (rc) return rc;
+    rc = check_errors(sub);
+    if (rc) return rc;
+    const uint64_t n_seed = sub->st_host->slots_used;
+    if (!depth || !n_seed) return KQ_OK;             // depth 0: the one pop meets seeds or inserts nodes, and nothing lies between a destination and its source
+    hipStream_t st = sub->stream;
+    SgFound fl;
+    const uint64_t block_bytes = kqbf::block_bytes(depth);
+    const uint32_t n_slots = kqbf::node_bound(depth);
+    const uint64_t batch = std::min<uint64_t>(n_seed, db->sg_batch ? db->sg_batch : std::max<uint64_t>(1, SG_BF_ARENA_BYTES / block_bytes));
+    uint8_t* d_arena = nullptr;
+    struct Res { SgBfState bf; SgExpandState ex; } res{};
+    Res* d_res = nullptr;
+    if (fl.mem.alloc((void**)&d_res, sizeof(Res)) != hipSuccess) return fail(KQ_ERR_NOMEM, "no device memory");
+    fl.d_state = &d_res->ex;
+    if (fl.mem.alloc((void**)&d_arena, batch * block_bytes) != hipSuccess)
+        return fail(KQ_ERR_NOMEM, "no device memory for the state blocks of %llu searches of depth %d", (unsigned long long)batch, depth);
+    rc = fl.room(sub, n_seed, 0, n_seed + 1);
+    if (rc) return rc;
+    // the sources: the seed k-mers with their merged subgraph entries (the counter of k_export becomes n_ents)
+    HIPC(hipMemsetAsync(d_res, 0, sizeof(Res), st));
+    hipLaunchKernelGGL(k_export, dim3(grid_for(sub, sub->n_slots(), 1024)), dim3(256), 0, st, sub->view(), (uint32_t)sub->map_count, 0u, (uint32_t)sub->map_count,
+                       fl.d_ents, fl.ents_cap, &d_res->ex.n_ents);
+    HIPC(hipGetLastError());
+    uint64_t n_ents = n_seed;
+    for (uint64_t lo = 0; lo < n_seed; lo += batch) {
+        const uint64_t n = std::min(batch, n_seed - lo);
+        HIPC(hipMemsetAsync(d_arena, 0xFF, n * block_bytes, st));      // the node indexes: every slot free (the rest of a block is written before it is read)
+        HIPC(hipMemsetAsync(&d_res->bf, 0, sizeof(SgBfState), st));
+        hipLaunchKernelGGL(k_sg_bf_search, dim3(grid_for(sub, n, 256)), dim3(256), 0, st, db->view(), sub->view(), (const kq_entry*)(fl.d_ents + lo), n, depth, cov_cutoff,
+                           d_arena, block_bytes, &d_res->bf);
+        HIPC(hipGetLastError());
+        // only the batch's total and the status words return to the host (with them the length of the found list after the batch before)
+        HIPC(hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        if (lo == 0 && res.ex.n_ents != n_seed) return fail(KQ_ERR_HIP, "best-first: %llu of %llu seeds listed", (unsigned long long)res.ex.n_ents, (unsigned long long)n_seed);
+        if (res.bf.err) return fail(KQ_ERR_HIP, "best-first: a search left its state block's bounds (error mask %u)", res.bf.err);      // cannot happen: 9 + 4 depth nodes
+        if (res.ex.err) return fail(KQ_ERR_HIP, "best-first: found list or visited set overflowed (%u)", res.ex.err);      // cannot happen: room()
+        n_ents = res.ex.n_ents;
+        if (!res.bf.n_found) continue;
+        rc = fl.room(sub, n_seed, n_ents, n_ents + res.bf.n_found);      // every discovered node may be a new k-mer
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_sg_bf_collect, dim3(grid_for(sub, n * n_slots, 256)), dim3(256), 0, st, db->view(), (const uint8_t*)d_arena, block_bytes, n, n_slots,
+                           fl.d_ents, fl.ents_cap, fl.d_vis, fl.vis_size - 1, &d_res->ex);
+        HIPC(hipGetLastError());
+    }
+    HIPC(hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (res.ex.err) return fail(KQ_ERR_HIP, "best-first: found list or visited set overflowed (%u)", res.ex.err);          // cannot happen: room()
+    n_ents = res.ex.n_ents;
+    const uint64_t n_found = n_ents - n_seed;
+    if (n_found) {                                   // after the last batch: the seed set was "seeds only" during every search (src/subgraph.cpp:453)
+        rc = reserve(sub, n_found, res.ex.n_instances);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_import, dim3(grid_for(sub, n_found, 256)), dim3(256), 0, st, sub->view(), (const kq_entry*)(fl.d_ents + n_seed), n_found);
         HIPC(hipGetLastError());
         rc = kq_sync(sub);
         if (rc) return rc;

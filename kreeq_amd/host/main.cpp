@@ -67,6 +67,8 @@ void kq_or_die(int rc) { if (rc != KQ_OK) die(std::string("Error: ") + kq_last_e
 // of entry by entry on the host; every file and stdout are byte-identical in both modes.  KQ_DB_TRACE=1 prints the wall
 // clock of the database steps of either mode to stderr.
 bool db_device() { static const bool on = [] { const char* e = getenv("KQ_DB_DEVICE"); return e && atoi(e) != 0; }(); return on; }
+// KQ_SUBGRAPH_DEVICE=1: `kreeq subgraph --traversal-algorithm best-first` searches on the GPU (kq_subgraph_best_first); off by default
+bool subgraph_device() { static const bool on = [] { const char* e = getenv("KQ_SUBGRAPH_DEVICE"); return e && atoi(e) != 0; }(); return on; }
 struct DbTrace {
     const char* what; double t0 = now_s(); uint64_t pcie = 0;
     explicit DbTrace(const char* w) : what(w) {}
@@ -898,10 +900,10 @@ int run(UserInput& ui) {
                 load_genome(ui.inSequence, e.genome);
                 verbose("Sequences loaded");
             }
+            static const bool trace = [] { const char* v = getenv("KQ_SUBGRAPH_TRACE"); return v && atoi(v) != 0; }();
             auto step = [t0 = now_s()](const char* what) mutable {      // KQ_SUBGRAPH_TRACE=1: wall clock of the steps to stderr
-                static const bool on = [] { const char* v = getenv("KQ_SUBGRAPH_TRACE"); return v && atoi(v) != 0; }();
                 const double t1 = now_s();
-                if (on) fprintf(stderr, "[subgraph] %s: %.3f s\n", what, t1 - t0);
+                if (trace) fprintf(stderr, "[subgraph] %s: %.3f s\n", what, t1 - t0);
                 t0 = t1;
             };
             kq_handle* sub = nullptr;
@@ -913,9 +915,16 @@ int run(UserInput& ui) {
             const bool best_first = ui.travAlgorithm == "best-first";
             const int depth = ui.kmerDepth != -1 ? ui.kmerDepth : best_first ? e.k : (e.k + 1) / 2;
             uint64_t n_added = 0;
-            if (best_first) n_added = subgraph_best_first(e.h, sub, e.k, e.map_count, depth, ui.covCutOff, [](const std::string& m) { verbose(m); });
+            // KQ_SUBGRAPH_DEVICE=1: the best-first searches run on the GPU, one per lane (kq_subgraph_best_first), instead of on the
+            // host in lockstep rounds of lookups; a depth above 255 keeps the host search (the device state block is sized for a uint8_t depth)
+            const bool bf_device = best_first && subgraph_device() && depth >= 0 && depth <= 255;
+            if (bf_device) {
+                kq_or_die(kq_subgraph_best_first(e.h, sub, depth, ui.covCutOff, &n_added));
+                verbose("Best-first: device search, " + std::to_string(n_added) + " k-mers added");
+            } else if (best_first) n_added = subgraph_best_first(e.h, sub, e.k, e.map_count, depth, ui.covCutOff, [](const std::string& m) { verbose("Best-first: host search"); verbose(m); });      // (the log is called once, at the end)
             else kq_or_die(kq_subgraph_expand(e.h, sub, depth, &n_added));
             step("expand");
+            if (best_first && trace) fprintf(stderr, "[subgraph] best-first ran as the %s search\n", bf_device ? "device" : "host");
             verbose(std::to_string(n_added) + " k-mers added by the search");
             verbose("Remove missing edges");                             // DBG::removeMissingEdges, :599-628
             kq_or_die(kq_subgraph_trim(sub, ui.covCutOff));

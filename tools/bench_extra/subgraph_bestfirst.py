@@ -1,0 +1,48 @@
+"""Wall clock of kq_subgraph_best_first ("Measured"): the database and the contig of
+tools/bench_extra/subgraph.py (100 Mbp shape, 30x 150 bp reads with 0.5 % substitutions, k = 21; a 1 Mbp contig of the genome
+with 1e-4 substitutions), best-first at the default depth k.  One run; one line.
+
+    python tools/bench_extra/subgraph_bestfirst.py [genome_mbp] [contig_mbp] [depth] [searches_per_batch]"""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import torch
+
+from kreeq_amd import KreeqDB, synth
+
+G = int(float(sys.argv[1]) * 1e6) if len(sys.argv) > 1 else 100_000_000
+CONTIG = int(float(sys.argv[2]) * 1e6) if len(sys.argv) > 2 else 1_000_000
+COV, L, K, ERR, ASM_ERR, BATCH_READS = 30, 150, 21, 0.005, 1e-4, 5_000_000
+DEPTH = int(sys.argv[3]) if len(sys.argv) > 3 else K
+BATCH = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+
+dev = torch.device("cuda", 0)
+n_reads = G * COV // L
+genome = synth.genome_dev(G, dev, seed=1)
+gen = torch.Generator(device=dev)
+gen.manual_seed(2)
+db = KreeqDB(K, 128, capacity_hint=int(1.1 * (G + n_reads * L * ERR * K)))
+db.set_option("trust_capacity", 1)
+t0 = time.perf_counter()
+for lo in range(0, n_reads, BATCH_READS):
+    batch = synth.reads_dev(genome, min(BATCH_READS, n_reads - lo), L, gen, err=ERR)
+    torch.cuda.synchronize(dev)                        # the batch was made on torch's stream, the handle counts on its own
+    db.count_batch_dev(batch.data_ptr(), batch.numel())
+    torch.cuda.synchronize(dev)
+    del batch
+db.sync()
+print(f"database: {db.summary()['distinct']} distinct k-mers of {n_reads} reads, counted in {time.perf_counter() - t0:.2f} s", flush=True)
+
+contig_codes, _ = synth.mutate_dev(genome[G // 2:G // 2 + CONTIG].clone(), ASM_ERR, seed=3)
+contig = synth.ascii_dev(contig_codes)
+torch.cuda.synchronize(dev)
+sub = KreeqDB(K, 128, capacity_hint=CONTIG + 1024)
+db.subgraph_seed_dev(sub, contig.data_ptr(), contig.numel())
+n_seed = sub.summary()["distinct"]
+db.set_option("subgraph_batch", BATCH)
+t0 = time.perf_counter()
+added = db.subgraph_best_first(sub, DEPTH, 0)
+t1 = time.perf_counter()
+print(f"best-first depth {DEPTH}: {n_seed} searches, {added} k-mers added: {(t1 - t0) * 1e3:.2f} ms", flush=True)
