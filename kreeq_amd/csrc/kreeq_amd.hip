@@ -20,6 +20,7 @@
 #include "../../include/kreeq_amd.h"
 #include "kq_device.h"
 #include "kq_partition.h"
+#include "kq_mem_host.h"
 #include "kq_roff_host.h"
 #include "kq_seg_gate_host.h"
 
@@ -58,89 +59,106 @@ struct Scrambled {
     void* p = nullptr; size_t bytes = 0, chunk = 0;
     std::vector<hipMemGenericAllocationHandle_t> hs;
     bool vmm = false;
+
+    Scrambled() = default;
+    Scrambled(const Scrambled&) = delete;
+    Scrambled& operator=(const Scrambled&) = delete;
+    Scrambled(Scrambled&& o) noexcept { swap(o); }
+    Scrambled& operator=(Scrambled&& o) noexcept { if (this != &o) { reset(); swap(o); } return *this; }
+    ~Scrambled() { reset(); }
+    void swap(Scrambled& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); std::swap(chunk, o.chunk); hs.swap(o.hs); std::swap(vmm, o.vmm); }
+    friend void swap(Scrambled& a, Scrambled& b) noexcept { a.swap(b); }
+
+    void reset() {
+        if (!p) return;
+        (void)hipDeviceSynchronize();
+        if (vmm) {
+            (void)hipMemUnmap(p, hs.size() * chunk);
+            for (auto& hnd : hs) (void)hipMemRelease(hnd);
+            (void)hipMemAddressFree(p, hs.size() * chunk);
+        } else (void)hipFree(p);
+        p = nullptr; bytes = chunk = 0; hs.clear(); vmm = false;
+    }
+    // `n` bytes (what was held goes first): the mapped form where `try_vmm` allows and the mapping calls succeed, else one plain
+    // block.  false, with the owner empty and the runtime's error cleared: no memory
+    bool alloc(size_t n, int device, bool try_vmm) {
+        reset();
+        if (try_vmm && map_chunks(n, device)) return true;
+        if (hipMalloc(&p, n) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
+        bytes = n; vmm = false;
+        return true;
+    }
+private:
+    bool map_chunks(size_t n_bytes, int device) {
+        static const size_t chunk_mb = getenv("KQ_SCRAMBLE_MB") ? (size_t)atoi(getenv("KQ_SCRAMBLE_MB")) : 2;      // 0: plain hipMalloc (A/B)
+        if (!chunk_mb) return false;
+        hipMemAllocationProp prop = {};
+        prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = device;
+        size_t gran = 0;
+        if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityMinimum) != hipSuccess || !gran) { (void)hipGetLastError(); return false; }
+        const size_t ck = ((chunk_mb << 20) + gran - 1) / gran * gran, n = (n_bytes + ck - 1) / ck;
+        void* base = nullptr;
+        if (hipMemAddressReserve(&base, n * ck, 0, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
+        std::vector<hipMemGenericAllocationHandle_t> fresh;
+        fresh.reserve(n);
+        bool ok = true;
+        for (size_t i = 0; i < n && ok; ++i) { hipMemGenericAllocationHandle_t hnd; ok = hipMemCreate(&hnd, ck, &prop, 0) == hipSuccess; if (ok) fresh.push_back(hnd); }
+        size_t mapped = 0;
+        if (ok) {
+            size_t mul = 7919;                                             // chunk i of the virtual range = physical chunk (i * mul + 13) mod n
+            while (std::gcd(mul, n) != 1) ++mul;
+            for (; mapped < n && ok; ++mapped) ok = hipMemMap((char*)base + mapped * ck, ck, 0, fresh[(mapped * mul + 13) % n], 0) == hipSuccess;
+            if (!ok) --mapped;
+        }
+        if (ok) {
+            hipMemAccessDesc acc = {};
+            acc.location = prop.location; acc.flags = hipMemAccessFlagsProtReadWrite;
+            ok = hipMemSetAccess(base, n * ck, &acc, 1) == hipSuccess;
+        }
+        if (!ok) {
+            (void)hipGetLastError();
+            if (mapped) (void)hipMemUnmap(base, mapped * ck);
+            for (auto& hnd : fresh) (void)hipMemRelease(hnd);
+            (void)hipMemAddressFree(base, n * ck);
+            return false;
+        }
+        p = base; bytes = n * ck; chunk = ck; hs.swap(fresh); vmm = true;
+        return true;
+    }
 };
-static void scr_free(Scrambled& b) {
-    if (!b.p) return;
-    (void)hipDeviceSynchronize();
-    if (b.vmm) {
-        (void)hipMemUnmap(b.p, b.hs.size() * b.chunk);
-        for (auto& hnd : b.hs) (void)hipMemRelease(hnd);
-        (void)hipMemAddressFree(b.p, b.hs.size() * b.chunk);
-    } else (void)hipFree(b.p);
-    b = Scrambled();
-}
-static bool scr_try_vmm(Scrambled& b, size_t bytes, int device) {
-    static const size_t chunk_mb = getenv("KQ_SCRAMBLE_MB") ? (size_t)atoi(getenv("KQ_SCRAMBLE_MB")) : 2;      // 0: plain hipMalloc (A/B)
-    if (!chunk_mb) return false;
-    hipMemAllocationProp prop = {};
-    prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = device;
-    size_t gran = 0;
-    if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityMinimum) != hipSuccess || !gran) { (void)hipGetLastError(); return false; }
-    const size_t chunk = ((chunk_mb << 20) + gran - 1) / gran * gran, n = (bytes + chunk - 1) / chunk;
-    void* base = nullptr;
-    if (hipMemAddressReserve(&base, n * chunk, 0, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
-    std::vector<hipMemGenericAllocationHandle_t> hs;
-    hs.reserve(n);
-    bool ok = true;
-    for (size_t i = 0; i < n && ok; ++i) { hipMemGenericAllocationHandle_t hnd; ok = hipMemCreate(&hnd, chunk, &prop, 0) == hipSuccess; if (ok) hs.push_back(hnd); }
-    size_t mapped = 0;
-    if (ok) {
-        size_t mul = 7919;                                             // chunk i of the virtual range = physical chunk (i * mul + 13) mod n
-        while (std::gcd(mul, n) != 1) ++mul;
-        for (; mapped < n && ok; ++mapped) ok = hipMemMap((char*)base + mapped * chunk, chunk, 0, hs[(mapped * mul + 13) % n], 0) == hipSuccess;
-        if (!ok) --mapped;
-    }
-    if (ok) {
-        hipMemAccessDesc acc = {};
-        acc.location = prop.location; acc.flags = hipMemAccessFlagsProtReadWrite;
-        ok = hipMemSetAccess(base, n * chunk, &acc, 1) == hipSuccess;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        if (mapped) (void)hipMemUnmap(base, mapped * chunk);
-        for (auto& hnd : hs) (void)hipMemRelease(hnd);
-        (void)hipMemAddressFree(base, n * chunk);
-        return false;
-    }
-    b.p = base; b.bytes = n * chunk; b.chunk = chunk; b.hs.swap(hs); b.vmm = true;
-    return true;
-}
 static int scr_ensure(Scrambled& b, size_t need, int device) {
     if (b.bytes >= need) return KQ_OK;
-    scr_free(b);
+    b.reset();                                                     // (before the new size is taken: the peak is one buffer)
     const size_t sz = need + std::min<size_t>(need / 4, (size_t)256 << 20) + 4096;
-    if (scr_try_vmm(b, sz, device)) return KQ_OK;
-    if (hipMalloc(&b.p, sz) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return fail(KQ_ERR_NOMEM, "partition scratch allocation failed"); }
-    b.bytes = sz; b.vmm = false;
+    if (!b.alloc(sz, device, true)) return fail(KQ_ERR_NOMEM, "partition scratch allocation failed");
     return KQ_OK;
 }
 
-// a device buffer grown on demand (ensure_buf); freed by kq_destroy, which sets the device first
-struct DevBuf { void* p = nullptr; size_t bytes = 0; };
 // the scratch of one partition plan (plan_alloc): record buffers + offsets, and the second record array of large plans (the
 // middle level's output)
-struct ScratchSet { DevBuf part; Scrambled part2; };
+struct ScratchSet { DevMem part; Scrambled part2; };
 
-struct kq_handle;
-static void arena_release(kq_handle* h);
+// Every resource below is an owner (kq_mem_host.h, Scrambled): `delete h` frees it, kq_destroy sets the device and drains the
+// streams first.  Members go in reverse order of declaration: the handle's own stream last.
 struct kq_handle {
     int device = 0, k = 0, map_count = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    Stream own_stream;
+    hipStream_t stream = nullptr;
     int n_cu = 256;
-    Slot* slots = nullptr;
+    DevMem slots;                    // Slot[n_slots()]
     uint64_t n_regions = 0;          // of the table's geometry (the scale of the hash -> region map)
     // window (multi-GPU shards, KQ_OPT_BUCKET_WINDOW / KQ_OPT_SHARD_WINDOW): only the regions of the hash-prefix buckets [win_lo, win_hi) are
     // allocated; `slots` is the allocation, view().slots the address region 0 would have
     uint32_t win_lo = 0, win_hi = 256;
     bool windowed = false;
-    HcSlot* hc = nullptr;
+    DevMem hc;                       // HcSlot[hc_cap]
     uint64_t hc_cap = 0;
-    uint32_t* rstart = nullptr;      // device: first top-32 hash value of every region (n_regions + 1 entries)
-    DevState* st = nullptr;          // device
-    DevState* st_host = nullptr;     // pinned mirror
+    DevMem rstart;                   // u32: first top-32 hash value of every region (n_regions + 1 entries)
+    DevMem st;                       // DevState
+    PinnedMem st_host;               // its pinned mirror
     // scratch (grown on demand)
-    DevBuf scratch;
-    DevBuf stage;                    // device staging for host-buffer entry points
+    DevMem scratch;
+    DevMem stage;                    // device staging for host-buffer entry points
     uint64_t kmers_bound = 0;        // upper bound of instances inserted (sizing the side table)
     uint64_t used_bound = 0;         // upper bound of occupied slots (skips the state read-back)
     uint64_t hc_check_at = 0;        // instance count from which the side table's fill is looked at again (reserve)
@@ -155,69 +173,70 @@ struct kq_handle {
     bool slice_user = false;             // set explicitly: no automatic enlargement
     uint32_t filt_lo = 0, filt_hi = 0;   // KQ_OPT_COUNT_MAP_RANGE (set to [0, map_count) at creation)
     bool profile = false;                // KQ_OPT_PROFILE: HIP events around the stages of the partitioned count
-    std::vector<std::pair<const char*, hipEvent_t>> marks;
+    std::vector<std::pair<const char*, Event>> marks;
     ScratchSet work, fork_work;                        // partitioned path: the scratch plans are carved from, and the fork's
     // Fork / join of the slices of ONE count call (see count_seq_dev): consecutive slices run their partition stages on two
     // internal streams with a scratch set each, so that slice j+1's P1 fills the issue slots slice j's levels leave idle.
     // `stream` is where launches go (a fork stream while a forked slice is being enqueued), `base` the handle's stream
     // (its own or the caller's): everything that reads the table or the device state runs there, behind a join.
     hipStream_t base = nullptr;
-    hipStream_t fork_stream[2] = {nullptr, nullptr};
+    Stream fork_stream[2];
     bool fork_busy[2] = {false, false};              // work enqueued on the fork stream that `base` has not been joined with
-    bool fork_stale[2] = {false, false};             // a table pass was enqueued on `base` since the fork stream last waited for one
     static constexpr int EV_RING = 64;
-    hipEvent_t ev_ring[EV_RING] = {};                // fork / join / pass events, used round-robin: an event is re-recorded only
+    Event ev_ring[EV_RING];                          // fork / join / pass events, used round-robin: an event is re-recorded only
     uint64_t ev_next = 0;                            // after the host has seen its previous use complete (ev_get)
-    hipEvent_t ev_pass = nullptr;                    // the last table pass on `base` (forked slices write into the arena it read)
     int overlap = 1;                                 // KQ_OPT_OVERLAP
     int kernel_set = 0;                              // KQ_OPT_KERNEL_SET (measurement only)
     // KQ_OPT_COUNT_MAP_PASSES: count matrices of resident batches, made for all map ranges by the first pass that scans a slice
     struct HistKey { const void* ab; const void* pinv; uint64_t lead, len, er_lo, er_hi; uint32_t g1, n_rng; int k;
                      bool operator==(const HistKey& o) const { return ab == o.ab && pinv == o.pinv && lead == o.lead && len == o.len && er_lo == o.er_lo && er_hi == o.er_hi && g1 == o.g1 && n_rng == o.n_rng && k == o.k; } };
-    struct HistEntry { HistKey key; unsigned long long* m1_all; size_t bytes; };
+    struct HistEntry { HistKey key; DevMem m1_all; };
     std::vector<HistEntry> hist_cache;
     size_t hist_cache_bytes = 0;
     int map_passes = 1;
     // pending record sets (see "pending sets" below): region-sorted records of earlier slices / batches that have not
     // been applied to the table yet; one k_count_regions pass takes them all
-    void* arena = nullptr; size_t arena_bytes = 0, arena_used = 0;
-    Scrambled arena_scr;                 // owns `arena` when it is a scrambled buffer (KQ_SCRAMBLE_ARENA)
-    P3Set* d_sets = nullptr;             // device array [P3_MAX_SETS]
+    Scrambled arena;                     // (a scrambled buffer from 1 GiB up: KQ_SCRAMBLE_ARENA)
+    size_t arena_bytes = 0, arena_used = 0;
+    DevMem d_sets;                       // P3Set[P3_MAX_SETS]
     P3Set pend_sets[P3_MAX_SETS] = {};   // the same on the host: the record pointers travel in k_count_regions_q4r's argument block
-    unsigned long long* tot = nullptr;   // [TOT_LINES][8] partial sums of a table pass (k_fold_totals), zero between passes
-    DevBuf roff;                         // region-major offset matrix of a table pass (k_p3_region_offsets): (allocated regions + 1) x P3_MAX_SETS u32
+    DevMem tot;                          // u64 [TOT_LINES][8] partial sums of a table pass (k_fold_totals), zero between passes
+    DevMem roff;                         // region-major offset matrix of a table pass (k_p3_region_offsets): (allocated regions + 1) x P3_MAX_SETS u32
     int n_pend = 0, pend_fmt = -1, pend_aux_fmt = 0;
     uint64_t pend_records = 0;           // upper bound of the records in the pending sets
     int64_t pend_budget = -1;            // KQ_OPT_PENDING_BYTES: -1 auto, 0 = apply every slice at once
     uint64_t table_passes = 0;           // k_count_regions passes so far
     // pipelined host ingest (kq_count_batch_async): copies on their own stream into a ring of device staging buffers
     static constexpr int IN_SLOTS = 3, IN_TICKETS = 512;
-    hipStream_t copy_stream = nullptr;
-    DevBuf in_buf[IN_SLOTS];
-    hipEvent_t in_consumed[IN_SLOTS] = {nullptr, nullptr, nullptr};      // the count that read the slot has been enqueued and finished
-    std::vector<hipEvent_t> in_copied;   // ring of "copy of ticket t done" events
+    Stream copy_stream;
+    DevMem in_buf[IN_SLOTS];
+    Event in_consumed[IN_SLOTS];         // the count that read the slot has been enqueued and finished
+    std::vector<Event> in_copied;        // ring of "copy of ticket t done" events
     uint64_t in_next = 0;
     std::mutex in_m;                     // kq_count_batch_async may be called from several threads: the calls take turns
     uint8_t in_bad[IN_TICKETS] = {};     // format (KQ_FASTX_*) whose rules the text of a ticket broke (kq_count_fastx_async), else 0
     // device FASTQ / FASTA parser (kq_fastx.h): unit summaries, the compact read batch of kq_count_fastx_dev and, per ring
     // slot, of kq_count_fastx_async (the slot's in_buf keeps the raw text), the chain's result and its page-locked mirror
-    DevBuf fx_units, fx_out, in_cmp[IN_SLOTS];
-    FxResult* fx_res = nullptr;          // device
-    FxResult* fx_res_host = nullptr;     // pinned
+    DevMem fx_units, fx_out, in_cmp[IN_SLOTS];
+    DevMem fx_res;                       // FxResult
+    PinnedMem fx_res_host;               // its pinned mirror
     int fx_bad = 0;                      // a counted text broke its format: reported by kq_sync until kq_clear
     bool hist_cache_off = false;         // the batch being counted lives in a library-owned buffer, which keeps its address and
                                          // changes its content: the address-keyed KQ_OPT_COUNT_MAP_PASSES cache must not see it
     bool test_fail_plan = false;         // KQ_OPT_TEST_FAIL_PLAN: the next partition plan fails with KQ_ERR_NOMEM (failure-path tests)
-    DevBuf hot;                          // k_count_regions' list of skewed regions
+    DevMem hot;                          // k_count_regions' list of skewed regions
     uint64_t sg_batch = 0;               // KQ_OPT_SUBGRAPH_BATCH: searches per batch of kq_subgraph_best_first, 0 = from the scratch budget
 
     TableView view() const {
-        TableView v; v.slots = slots - (reg_lo() << REGION_SHIFT); v.n_regions = n_regions; v.hc = hc; v.hc_mask = hc_cap - 1; v.st = st; v.k = (uint32_t)k;
+        TableView v; v.slots = slots.as<Slot>() - (reg_lo() << REGION_SHIFT); v.n_regions = n_regions; v.hc = hc.as<HcSlot>(); v.hc_mask = hc_cap - 1; v.st = d_state(); v.k = (uint32_t)k;
         v.reg_lo = reg_lo(); v.reg_hi = reg_hi();
         v.rps = k >= HI_K ? (uint32_t)(n_regions >> 8) : 0u;
-        v.rstart = rstart;
+        v.rstart = rstart.as<uint32_t>();
         return v;
     }
+    DevState* d_state() const { return st.as<DevState>(); }
+    DevState* host_state() const { return st_host.as<DevState>(); }
+    FxResult* fx_host() const { return fx_res_host.as<FxResult>(); }
     uint64_t reg_lo() const { return windowed ? (uint64_t)win_lo * (n_regions >> 8) : 0; }
     uint64_t reg_hi() const { return windowed ? (uint64_t)win_hi * (n_regions >> 8) : n_regions; }
     uint64_t n_alloc_regions() const { return reg_hi() - reg_lo(); }
@@ -232,10 +251,10 @@ static int flush_pending(kq_handle* h);
 // not: that bounds how far the host runs ahead to EV_RING forks / joins).  Re-recording an event that a queued
 // hipStreamWaitEvent still refers to is exactly what this avoids.
 static int ev_get(kq_handle* h, hipEvent_t* out) {
-    hipEvent_t& e = h->ev_ring[h->ev_next++ % kq_handle::EV_RING];
-    if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    else HIPC(hipEventSynchronize(e));
-    *out = e;
+    Event& e = h->ev_ring[h->ev_next++ % kq_handle::EV_RING];
+    if (!e) HIPC(e.create(hipEventDisableTiming));
+    else HIPC(hipEventSynchronize(e.get()));
+    *out = e.get();
     return KQ_OK;
 }
 // `base` waits for everything the fork streams have been given
@@ -243,7 +262,7 @@ static int join_forks(kq_handle* h) {
     for (int w = 0; w < 2; ++w) {
         if (!h->fork_busy[w]) continue;
         hipEvent_t e; int rc = ev_get(h, &e); if (rc) return rc;
-        HIPC(hipEventRecord(e, h->fork_stream[w]));
+        HIPC(hipEventRecord(e, h->fork_stream[w].get()));
         HIPC(hipStreamWaitEvent(h->base, e, 0));
         h->fork_busy[w] = false;
     }
@@ -260,20 +279,6 @@ static int grid_for(const kq_handle* h, uint64_t work_items, int per_block, int 
     return (int)blocks;
 }
 
-static void arena_release(kq_handle* h) {
-    if (!h->arena) return;
-    if (h->arena_scr.p) scr_free(h->arena_scr); else (void)hipFree(h->arena);
-    h->arena = nullptr; h->arena_bytes = 0;
-}
-static int ensure_buf(DevBuf& b, size_t need) {
-    if (b.bytes >= need) return KQ_OK;
-    if (b.p) { HIPC(hipFree(b.p)); b = DevBuf(); }
-    size_t sz = need + std::min<size_t>(need / 4, (size_t)256 << 20) + 4096;      // geometric growth for small buffers, bounded slack for multi-GB ones
-    HIPC(hipMalloc(&b.p, sz));
-    b.bytes = sz;
-    return KQ_OK;
-}
-
 static void clear_words(kq_handle* h, void* p, uint32_t words_per_slot, uint64_t n_slots) {
     const uint64_t n_pairs = n_slots * words_per_slot / 2;      // both table sizes make this exact
     hipLaunchKernelGGL(k_clear_slots, dim3(grid_for(h, n_pairs, 256)), dim3(256), 0, h->stream, (ulonglong2*)p, words_per_slot, n_pairs);
@@ -283,32 +288,26 @@ static void clear_main(kq_handle* h, Slot* p, uint64_t n_slots) { (void)hipMemse
 // lazy kq_clear: give the slot array its empty image now (every table user except the partitioned count)
 static void materialize(kq_handle* h) {
     if (!h->slots_dirty) return;
-    clear_main(h, h->slots, h->n_slots());
+    clear_main(h, h->slots.as<Slot>(), h->n_slots());
     h->slots_dirty = false;
 }
-// `alloc_regions` of the n_regions of the geometry get memory (all of them unless the table is a window)
-static int alloc_main(kq_handle* h, uint64_t n_regions, uint64_t alloc_regions, Slot** out, uint32_t** rstart_out) {
-    Slot* p = nullptr;
-    uint32_t* rs = nullptr;
-    size_t bytes = (size_t)(alloc_regions << REGION_SHIFT) * sizeof(Slot);
-    HIPC(hipMalloc((void**)&p, bytes));
-    if (hipMalloc((void**)&rs, (size_t)(n_regions + 1) * sizeof(uint32_t)) != hipSuccess) { (void)hipFree(p); return fail(KQ_ERR_NOMEM, "region index allocation failed"); }
-    clear_main(h, p, alloc_regions << REGION_SHIFT);
-    hipLaunchKernelGGL(k_region_starts, dim3(grid_for(h, n_regions + 1, 256)), dim3(256), 0, h->stream, rs, n_regions);
-    *out = p; *rstart_out = rs;
+// `alloc_regions` of the n_regions of the geometry get memory (all of them unless the table is a window).  `slots` and `rstart`
+// are the caller's (empty) owners: the handle's own at creation, locals where a table replaces one
+static int alloc_main(kq_handle* h, uint64_t n_regions, uint64_t alloc_regions, DevMem& slots, DevMem& rstart) {
+    HIPC(slots.alloc((size_t)(alloc_regions << REGION_SHIFT) * sizeof(Slot)));
+    if (rstart.alloc((size_t)(n_regions + 1) * sizeof(uint32_t)) != hipSuccess) { slots.reset(); return fail(KQ_ERR_NOMEM, "region index allocation failed"); }
+    clear_main(h, slots.as<Slot>(), alloc_regions << REGION_SHIFT);
+    hipLaunchKernelGGL(k_region_starts, dim3(grid_for(h, n_regions + 1, 256)), dim3(256), 0, h->stream, rstart.as<uint32_t>(), n_regions);
     return KQ_OK;
 }
-static int alloc_hc(kq_handle* h, uint64_t cap, HcSlot** out) {
-    HcSlot* p = nullptr;
-    size_t bytes = (size_t)cap * sizeof(HcSlot);
-    HIPC(hipMalloc((void**)&p, bytes));
-    clear_words(h, p, sizeof(HcSlot) / 8, cap);
-    *out = p;
+static int alloc_hc(kq_handle* h, uint64_t cap, DevMem& hc) {
+    HIPC(hc.alloc((size_t)cap * sizeof(HcSlot)));
+    clear_words(h, hc.get(), sizeof(HcSlot) / 8, cap);
     return KQ_OK;
 }
 
 static int read_state_raw(kq_handle* h) {
-    HIPC(hipMemcpyAsync(h->st_host, h->st, sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
+    HIPC(hipMemcpyAsync(h->host_state(), h->d_state(), sizeof(DevState), hipMemcpyDeviceToHost, h->stream));
     HIPC(hipStreamSynchronize(h->stream));
     return KQ_OK;
 }
@@ -320,10 +319,10 @@ static int read_state(kq_handle* h) {
 static int check_errors(kq_handle* h) {
     int rc = read_state(h);
     if (rc) return rc;
-    if (h->st_host->err_table_full) return fail(KQ_ERR_TABLE_FULL, "k-mer table region overflow (slots %llu / %llu)",
-                                                 (unsigned long long)h->st_host->slots_used, (unsigned long long)h->n_slots());
-    if (h->st_host->err_hc_full) return fail(KQ_ERR_TABLE_FULL, "high-copy side table overflow (%llu / %llu)",
-                                              (unsigned long long)h->st_host->hc_used, (unsigned long long)h->hc_cap);
+    if (h->host_state()->err_table_full) return fail(KQ_ERR_TABLE_FULL, "k-mer table region overflow (slots %llu / %llu)",
+                                                 (unsigned long long)h->host_state()->slots_used, (unsigned long long)h->n_slots());
+    if (h->host_state()->err_hc_full) return fail(KQ_ERR_TABLE_FULL, "high-copy side table overflow (%llu / %llu)",
+                                              (unsigned long long)h->host_state()->hc_used, (unsigned long long)h->hc_cap);
     return KQ_OK;
 }
 
@@ -335,34 +334,32 @@ static int grow_main(kq_handle* h, uint64_t need_slots) {
     uint64_t want = h->n_slots(), new_regions = h->n_regions;       // doubling keeps every multiple the geometry (and a window) needs
     while (want < need_slots) { want *= 2; new_regions *= 2; }
     if (new_regions >= (1ull << 32)) return fail(KQ_ERR_TABLE_FULL, "cannot grow k-mer table to %llu slots: region index overflow", (unsigned long long)want);
-    Slot* fresh = nullptr;
-    uint32_t* fresh_rs = nullptr;
-    int rc = alloc_main(h, new_regions, want >> REGION_SHIFT, &fresh, &fresh_rs);
+    // the new table in local owners; after the swap they hold the old one, which goes at scope exit on every way out: behind
+    // the stream synchronisation below (the rehash reads it), or, if that fails, through a free that waits for the device
+    DevMem slots, rstart;
+    int rc = alloc_main(h, new_regions, want >> REGION_SHIFT, slots, rstart);
     if (rc) return rc == KQ_ERR_NOMEM ? fail(KQ_ERR_TABLE_FULL, "cannot grow k-mer table to %llu slots: out of device memory",
                                              (unsigned long long)want) : rc;
-    Slot* old = h->slots; const uint64_t n_old = h->n_slots();
+    const uint64_t n_old = h->n_slots();
     const TableView old_view = h->view();
-    uint32_t* old_rs = h->rstart;
-    h->slots = fresh; h->n_regions = new_regions; h->rstart = fresh_rs;
+    slots.swap(h->slots); rstart.swap(h->rstart);
+    h->n_regions = new_regions;
     if (h->slots_dirty) h->slots_dirty = false;     // lazily cleared table: nothing to move, and the fresh array is clean
     else hipLaunchKernelGGL(k_rehash, dim3(grid_for(h, n_old, 256)), dim3(256), 0, h->stream, h->view(), old_view);
     HIPC(hipStreamSynchronize(h->stream));
-    HIPC(hipFree(old));
-    if (old_rs) HIPC(hipFree(old_rs));
     return KQ_OK;
 }
 static int grow_hc(kq_handle* h, uint64_t need) {
     uint64_t want = h->hc_cap;
     while (want < need) want *= 2;
-    HcSlot* fresh = nullptr;
-    int rc = alloc_hc(h, want, &fresh);
+    DevMem hc;                                      // the new side table; the old one after the swap (see grow_main)
+    int rc = alloc_hc(h, want, hc);
     if (rc) return rc;
-    HcSlot* old = h->hc; const uint64_t n_old = h->hc_cap;
-    h->hc = fresh; h->hc_cap = want;
-    HIPC(hipMemsetAsync(&h->st->hc_used, 0, sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(k_rehash_hc, dim3(grid_for(h, n_old, 256)), dim3(256), 0, h->stream, h->view(), old, n_old);
+    const uint64_t n_old = h->hc_cap;
+    hc.swap(h->hc); h->hc_cap = want;
+    HIPC(hipMemsetAsync(&h->d_state()->hc_used, 0, sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(k_rehash_hc, dim3(grid_for(h, n_old, 256)), dim3(256), 0, h->stream, h->view(), hc.as<HcSlot>(), n_old);
     HIPC(hipStreamSynchronize(h->stream));
-    HIPC(hipFree(old));
     return KQ_OK;
 }
 
@@ -380,7 +377,7 @@ static int reserve(kq_handle* h, uint64_t extra, uint64_t extra_instances) {
         if (need > h->n_slots()) {
             rc = read_state(h); if (rc) return rc;
             state_read = true;
-            h->used_bound = h->st_host->slots_used;
+            h->used_bound = h->host_state()->slots_used;
             need = (uint64_t)((double)(h->used_bound + extra) / 0.85) + REGION_SLOTS;
             if (need > h->n_slots()) { rc = grow_main(h, need); if (rc) return rc; }
         }
@@ -397,7 +394,7 @@ static int reserve(kq_handle* h, uint64_t extra, uint64_t extra_instances) {
     if (bound > (1ull << 23)) need_hc = HC_CAP_BIG;
     if (bound > (1ull << 23) && h->kmers_bound >= h->hc_check_at && h->n_pend == 0) {
         if (!state_read) { rc = read_state_raw(h); if (rc) return rc; }
-        need_hc = std::max<uint64_t>(need_hc, 8 * h->st_host->hc_used);
+        need_hc = std::max<uint64_t>(need_hc, 8 * h->host_state()->hc_used);
         h->hc_check_at = 2 * h->kmers_bound;
     }
     if (need_hc > h->hc_cap) { rc = grow_hc(h, need_hc); if (rc) return rc; }
@@ -412,10 +409,9 @@ static inline void aligned_view(const char* d, const uint8_t** ab, uint64_t* lea
 }
 
 static int stage_in(kq_handle* h, const void* host, size_t bytes, void** dev) {
-    int rc = ensure_buf(h->stage, bytes + 64);
-    if (rc) return rc;
-    if (bytes) HIPC(hipMemcpyAsync(h->stage.p, host, bytes, hipMemcpyHostToDevice, h->stream));
-    *dev = h->stage.p;
+    HIPC(h->stage.ensure(bytes + 64));
+    if (bytes) HIPC(hipMemcpyAsync(h->stage.get(), host, bytes, hipMemcpyHostToDevice, h->stream));
+    *dev = h->stage.get();
     return KQ_OK;
 }
 
@@ -509,14 +505,11 @@ static int set_window(kq_handle* h, uint32_t lo, uint32_t hi, bool shard = false
     // the new table first: a failed allocation leaves the handle as it was
     const bool windowed = !(lo == 0 && hi == 256);
     const uint64_t alloc_new = windowed ? (uint64_t)(hi - lo) * (virt >> 8) : virt;
-    Slot* fresh = nullptr;
-    uint32_t* fresh_rs = nullptr;
-    int rc = alloc_main(h, virt, alloc_new, &fresh, &fresh_rs);
+    DevMem slots, rstart;
+    int rc = alloc_main(h, virt, alloc_new, slots, rstart);
     if (rc) return rc;
     HIPC(hipStreamSynchronize(h->stream));
-    if (h->slots) (void)hipFree(h->slots);
-    if (h->rstart) (void)hipFree(h->rstart);
-    h->slots = fresh; h->rstart = fresh_rs;
+    slots.swap(h->slots); rstart.swap(h->rstart);          // (the old table goes at scope exit)
     h->n_regions = virt; h->win_lo = lo; h->win_hi = hi; h->windowed = windowed;
     h->slots_dirty = false;
     return KQ_OK;
@@ -539,21 +532,21 @@ int kq_create(kq_handle** out, int device, int k, int map_count, uint64_t capaci
     if (!h) return fail(KQ_ERR_NOMEM, "host allocation failed");
     h->device = device; h->k = k; h->map_count = map_count; h->n_cu = prop.multiProcessorCount;
     h->filt_hi = (uint32_t)map_count;
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
+    hipError_t e = h->own_stream.create(hipStreamNonBlocking);
     if (e != hipSuccess) { delete h; return fail(KQ_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-    h->stream = h->base = h->own_stream;
+    h->stream = h->base = h->own_stream.get();
     int rc = KQ_OK;
     do {
-        if (hipMalloc((void**)&h->st, sizeof(DevState)) != hipSuccess || hipHostMalloc((void**)&h->st_host, sizeof(DevState)) != hipSuccess) {
+        if (h->st.alloc(sizeof(DevState)) != hipSuccess || h->st_host.alloc(sizeof(DevState)) != hipSuccess) {
             rc = fail(KQ_ERR_NOMEM, "state allocation failed"); break;
         }
-        (void)hipMemsetAsync(h->st, 0, sizeof(DevState), h->stream);
+        (void)hipMemsetAsync(h->d_state(), 0, sizeof(DevState), h->stream);
         uint64_t slots = (uint64_t)((double)(capacity_hint ? capacity_hint : (1u << 20)) / 0.7);   // load <= 0.7 at the hinted size
         const uint64_t regions = round_regions((slots + REGION_SLOTS - 1) >> REGION_SHIFT, k);
-        rc = alloc_main(h, regions, regions, &h->slots, &h->rstart); if (rc) break;
+        rc = alloc_main(h, regions, regions, h->slots, h->rstart); if (rc) break;
         h->n_regions = regions;
         uint64_t hc = 1u << 16;
-        rc = alloc_hc(h, hc, &h->hc); if (rc) break;
+        rc = alloc_hc(h, hc, h->hc); if (rc) break;
         h->hc_cap = hc;
         if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(KQ_ERR_HIP, "table initialisation failed"); break; }
     } while (0);
@@ -562,39 +555,13 @@ int kq_create(kq_handle** out, int device, int k, int map_count, uint64_t capaci
     return KQ_OK;
 }
 
+// set the device, drain the streams, delete: every member of the handle frees what it holds
 void kq_destroy(kq_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->slots) (void)hipFree(h->slots);
-    if (h->rstart) (void)hipFree(h->rstart);
-    if (h->hc) (void)hipFree(h->hc);
-    if (h->st) (void)hipFree(h->st);
-    if (h->st_host) (void)hipHostFree(h->st_host);
-    if (h->scratch.p) (void)hipFree(h->scratch.p);
-    if (h->stage.p) (void)hipFree(h->stage.p);
-    if (h->work.part.p) (void)hipFree(h->work.part.p);
-    scr_free(h->work.part2); scr_free(h->fork_work.part2);
-    for (auto& e : h->hist_cache) (void)hipFree(e.m1_all);
-    for (int w = 0; w < 2; ++w) { if (h->fork_stream[w]) { (void)hipStreamSynchronize(h->fork_stream[w]); (void)hipStreamDestroy(h->fork_stream[w]); } }
-    if (h->fork_work.part.p) (void)hipFree(h->fork_work.part.p);
-    for (auto e : h->ev_ring) if (e) (void)hipEventDestroy(e);
-    if (h->ev_pass) (void)hipEventDestroy(h->ev_pass);
-    for (int i = 0; i < kq_handle::IN_SLOTS; ++i) { if (h->in_buf[i].p) (void)hipFree(h->in_buf[i].p); if (h->in_consumed[i]) (void)hipEventDestroy(h->in_consumed[i]); }
-    for (auto e : h->in_copied) (void)hipEventDestroy(e);
-    for (int i = 0; i < kq_handle::IN_SLOTS; ++i) if (h->in_cmp[i].p) (void)hipFree(h->in_cmp[i].p);
-    if (h->fx_units.p) (void)hipFree(h->fx_units.p);
-    if (h->fx_out.p) (void)hipFree(h->fx_out.p);
-    if (h->fx_res) (void)hipFree(h->fx_res);
-    if (h->fx_res_host) (void)hipHostFree(h->fx_res_host);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    arena_release(h);
-    if (h->d_sets) (void)hipFree(h->d_sets);
-    if (h->roff.p) (void)hipFree(h->roff.p);
-    if (h->tot) (void)hipFree(h->tot);
-    if (h->hot.p) (void)hipFree(h->hot.p);
-    marks_reset(h);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    for (auto& s : h->fork_stream) if (s) (void)hipStreamSynchronize(s.get());
+    if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream.get());
     delete h;
 }
 
@@ -602,8 +569,8 @@ int kq_clear(kq_handle* h) {
     if (!h) return fail(KQ_ERR_INVALID, "null handle");
     HIPC(hipSetDevice(h->device));
     h->slots_dirty = true;           // the 24 B/slot clear is folded into the next partitioned count (k_count_regions writes every region); anything else materialises it first
-    clear_words(h, h->hc, sizeof(HcSlot) / 8, h->hc_cap);
-    HIPC(hipMemsetAsync(h->st, 0, sizeof(DevState), h->stream));
+    clear_words(h, h->hc.get(), sizeof(HcSlot) / 8, h->hc_cap);
+    HIPC(hipMemsetAsync(h->d_state(), 0, sizeof(DevState), h->stream));
     h->kmers_bound = 0;
     h->used_bound = 0;
     h->hc_check_at = 0;
@@ -616,7 +583,7 @@ int kq_clear(kq_handle* h) {
 int kq_set_stream(kq_handle* h, void* s) {
     if (!h) return fail(KQ_ERR_INVALID, "null handle");
     HIPC(hipStreamSynchronize(h->stream));
-    h->stream = h->base = s ? (hipStream_t)s : h->own_stream;
+    h->stream = h->base = s ? (hipStream_t)s : h->own_stream.get();
     return KQ_OK;
 }
 int kq_set_option(kq_handle* h, int option, int64_t value) {
@@ -646,7 +613,6 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
             if (value != 1 && value != 2 && value != 4 && value != 8) return fail(KQ_ERR_INVALID, "KQ_OPT_COUNT_MAP_PASSES must be 1, 2, 4 or 8");
             if ((h->map_count & (h->map_count - 1)) != 0 || value > h->map_count) return fail(KQ_ERR_INVALID, "KQ_OPT_COUNT_MAP_PASSES needs a power-of-two map count");
             HIPC(hipStreamSynchronize(h->stream));
-            for (auto& e : h->hist_cache) (void)hipFree(e.m1_all);
             h->hist_cache.clear(); h->hist_cache_bytes = 0;
             h->map_passes = (int)value; return KQ_OK;
         }
@@ -660,7 +626,7 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
             if (value < -1) return fail(KQ_ERR_INVALID, "KQ_OPT_PENDING_BYTES must be -1 (auto), 0 (off) or a byte count");
             int rc = flush_pending(h);
             if (rc) return rc;
-            if (h->arena && value != h->pend_budget) { HIPC(hipStreamSynchronize(h->stream)); arena_release(h); }
+            if (h->arena.p && value != h->pend_budget) { HIPC(hipStreamSynchronize(h->stream)); h->arena.reset(); h->arena_bytes = 0; }
             h->pend_budget = value; return KQ_OK;
         }
         case KQ_OPT_BUCKET_WINDOW:
@@ -685,7 +651,7 @@ int kq_get_profile(kq_handle* h, char* buf, uint64_t cap) {
     std::string out;
     for (size_t i = 1; i < h->marks.size(); ++i) {
         float ms = 0;
-        HIPC(hipEventElapsedTime(&ms, h->marks[i - 1].second, h->marks[i].second));
+        HIPC(hipEventElapsedTime(&ms, h->marks[i - 1].second.get(), h->marks[i].second.get()));
         char tmp[96];
         snprintf(tmp, sizeof tmp, "%s%s=%.4f", out.empty() ? "" : ";", h->marks[i].first, ms);
         out += tmp;
@@ -713,10 +679,10 @@ int kq_get_info(kq_handle* h, kq_info* out) {
     HIPC(hipSetDevice(h->device));
     int rc = read_state(h);
     if (rc) return rc;
-    out->kmers_counted = h->st_host->kmers_added;
-    out->slots_used = h->st_host->slots_used;
+    out->kmers_counted = h->host_state()->kmers_added;
+    out->slots_used = h->host_state()->slots_used;
     out->slots_total = h->n_slots();
-    out->hc_used = h->st_host->hc_used;
+    out->hc_used = h->host_state()->hc_used;
     out->hc_total = h->hc_cap;
     out->table_bytes = h->n_slots() * sizeof(Slot) + h->hc_cap * sizeof(HcSlot);
     out->table_passes = h->table_passes;
@@ -799,9 +765,8 @@ static int plan_alloc(kq_handle* h, PartPlan* p, uint64_t n_max, uint64_t n_tile
     const bool split2 = (rec_words + aux_words) * 8 >= ((size_t)512 << 20);
     if (split2) { int rc2 = scr_ensure(h->work.part2, (size_t)(rec_words + aux_words) * 8, h->device); if (rc2) return rc2; }
     const size_t words = (size_t)((split2 ? 1 : 2) * (rec_words + aux_words) + p->m1_n + 2 * (seg_max + 2) + p->groups_n + p->sums_n + 4 + (p->R + 2) + (p->m2_n + 1) / 2);
-    int rc = ensure_buf(h->work.part, words * 8);
-    if (rc) return rc;
-    p->recs1 = (uint64_t*)h->work.part.p;
+    HIPC(h->work.part.ensure(words * 8));
+    p->recs1 = h->work.part.as<uint64_t>();
     p->aux1 = (uint8_t*)(p->recs1 + rec_words);
     uint64_t* rest = (uint64_t*)(p->aux1 + aux_words * 8);
     if (split2) { p->recs2 = (uint64_t*)h->work.part2.p; p->aux2 = (uint8_t*)(p->recs2 + rec_words); }
@@ -832,15 +797,12 @@ static void scan_u64(kq_handle* h, unsigned long long* a, uint64_t n, unsigned l
 // stage marker of the last partitioned count (KQ_OPT_PROFILE): one HIP event per call, on the handle's stream
 static void mark(kq_handle* h, const char* name) {
     if (!h->profile) return;
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return;
-    (void)hipEventRecord(e, h->stream);
-    h->marks.emplace_back(name, e);
+    Event e;
+    if (e.create(hipEventDefault) != hipSuccess) return;
+    (void)hipEventRecord(e.get(), h->stream);
+    h->marks.emplace_back(name, std::move(e));
 }
-static void marks_reset(kq_handle* h) {
-    for (auto& m : h->marks) (void)hipEventDestroy(m.second);
-    h->marks.clear();
-}
+static void marks_reset(kq_handle* h) { h->marks.clear(); }
 
 static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t* ab, uint64_t lead, uint64_t len, EmitRange er, uint64_t* out,
                    uint8_t* out_aux, int aux_fmt, const uint16_t* pinv = nullptr /*packed input: ab = the code words (tile_fetch)*/) {
@@ -858,10 +820,10 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     auto cached_hist = [&](const kq_handle::HistKey& key, size_t bytes, auto launch) -> kq_handle::HistEntry* {
         for (auto& e : h->hist_cache) if (e.key == key) return &e;
         if (h->hist_cache_bytes + bytes > ((size_t)4 << 30)) return nullptr;
-        unsigned long long* buf = nullptr;
-        if (hipMalloc((void**)&buf, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        launch(buf);
-        h->hist_cache.push_back(kq_handle::HistEntry{key, buf, bytes});
+        DevMem buf;
+        if (buf.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        launch(buf.as<unsigned long long>());
+        h->hist_cache.push_back(kq_handle::HistEntry{key, std::move(buf)});
         h->hist_cache_bytes += bytes;
         return &h->hist_cache.back();
     };
@@ -877,7 +839,7 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
                 else hipLaunchKernelGGL((k_p1_hist<5, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
             });
             if (ent) {
-                (void)hipMemcpyAsync(p->m1, (const char*)ent->m1_all + rr * block, block, hipMemcpyDeviceToDevice, h->stream);
+                (void)hipMemcpyAsync(p->m1, ent->m1_all.as<char>() + rr * block, block, hipMemcpyDeviceToDevice, h->stream);
                 have_hist = true;
             }
         }
@@ -892,7 +854,7 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
             else hipLaunchKernelGGL((k_p1_hist<2, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);      // (any k: hash-remainder records too)
         });
         if (ent) {
-            (void)hipMemcpyAsync(p->m1, ent->m1_all, block, hipMemcpyDeviceToDevice, h->stream);
+            (void)hipMemcpyAsync(p->m1, ent->m1_all.get(), block, hipMemcpyDeviceToDevice, h->stream);
             if (cfg.win_lo) (void)hipMemsetAsync(p->m1, 0, (size_t)cfg.win_lo * row, h->stream);
             if (cfg.win_hi < (1u << NARROW_CBITS)) (void)hipMemsetAsync((char*)p->m1 + (size_t)cfg.win_hi * row, 0, (size_t)((1u << NARROW_CBITS) - cfg.win_hi) * row, h->stream);
             have_hist = true;
@@ -1027,7 +989,7 @@ static LevelCfg level_narrow(const PartCfg& cfg, uint32_t sub_bits = 0, bool mid
     return lv;
 }
 // FMT_TIGHT output of the last split level (count path only: the lookup kernels read 5-byte records)
-static bool tight_ok(const kq_handle* h, const PartPlan& p) { return p.fmt == FMT_NARROW && p.R >= TIGHT_MIN_REGIONS && h->rstart != nullptr; }
+static bool tight_ok(const kq_handle* h, const PartPlan& p) { return p.fmt == FMT_NARROW && p.R >= TIGHT_MIN_REGIONS && (bool)h->rstart; }
 static LevelCfg level_flat_to_coarse(const PartCfg& cfg) {
     LevelCfg lv; lv.n_regions = cfg.n_regions; lv.n_seg = 1; lv.nb = cfg.n_coarse; lv.seg_shift = 32; lv.out_shift = cfg.g_shift; lv.in_raw = 0; lv.k = 0; lv.narrow = 0; lv.top8 = 0;
     lv.nr_shift = lv.nr_rps = lv.nr_sub = lv.nr_inv = 0; lv.nr_div = 1;
@@ -1095,15 +1057,13 @@ static int arena_take(kq_handle* h, uint64_t n_max, uint64_t R, Dest* d) {
         if (budget <= h->arena_bytes && need <= h->arena_bytes) budget = 0;         // at its ceiling already
         if (budget && budget < need) return KQ_OK;
         if (budget) {
-            if (h->arena) { HIPC(hipStreamSynchronize(h->stream)); HIPC(hipStreamSynchronize(h->base)); arena_release(h); }
+            if (h->arena.p) { HIPC(hipStreamSynchronize(h->stream)); HIPC(hipStreamSynchronize(h->base)); h->arena.reset(); h->arena_bytes = 0; }
             static const bool scramble_arena = !getenv("KQ_SCRAMBLE_ARENA") || atoi(getenv("KQ_SCRAMBLE_ARENA")) != 0;      // (0: plain hipMalloc, for A/B)
-            if (scramble_arena && budget >= ((size_t)1 << 30) && scr_try_vmm(h->arena_scr, budget, h->device)) h->arena = h->arena_scr.p;
-            else
-            if (hipMalloc(&h->arena, budget) != hipSuccess) { (void)hipGetLastError(); h->arena = nullptr; return KQ_OK; }
+            if (!h->arena.alloc(budget, h->device, scramble_arena && budget >= ((size_t)1 << 30))) return KQ_OK;      // no memory is no error: the slice stays in the scratch
             h->arena_bytes = budget; h->arena_used = 0;
         }
     }
-    uint8_t* set = (uint8_t*)h->arena + h->arena_used;
+    uint8_t* set = (uint8_t*)h->arena.p + h->arena_used;
     d->recs = (uint64_t*)set;
     d->aux = lay.has_aux ? set + lay.aux_off : nullptr;
     d->base = (unsigned long long*)(set + lay.base_off);
@@ -1117,8 +1077,8 @@ static int pend_add(kq_handle* h, const P3Set& set, int fmt, int aux_fmt) {
         int rc = flush_pending(h);
         if (rc) return rc;
     }
-    if (!h->d_sets) HIPC(hipMalloc((void**)&h->d_sets, sizeof(P3Set) * P3_MAX_SETS));
-    hipLaunchKernelGGL(k_p3set, dim3(1), dim3(1), 0, h->stream, h->d_sets, h->n_pend, set);
+    if (!h->d_sets) HIPC(h->d_sets.alloc(sizeof(P3Set) * P3_MAX_SETS));
+    hipLaunchKernelGGL(k_p3set, dim3(1), dim3(1), 0, h->stream, h->d_sets.as<P3Set>(), h->n_pend, set);
     h->pend_sets[h->n_pend] = set;
     h->pend_fmt = fmt; h->pend_aux_fmt = aux_fmt;
     ++h->n_pend;
@@ -1137,7 +1097,7 @@ static int flush_pending(kq_handle* h) {
     if (!rc && h->fork_stream[0]) {
         hipEvent_t e; rc = ev_get(h, &e);
         if (!rc && hipEventRecord(e, h->base) != hipSuccess) rc = fail(KQ_ERR_HIP, "hipEventRecord failed");
-        for (int w = 0; w < 2 && !rc; ++w) if (hipStreamWaitEvent(h->fork_stream[w], e, 0) != hipSuccess) rc = fail(KQ_ERR_HIP, "hipStreamWaitEvent failed");
+        for (int w = 0; w < 2 && !rc; ++w) if (hipStreamWaitEvent(h->fork_stream[w].get(), e, 0) != hipSuccess) rc = fail(KQ_ERR_HIP, "hipStreamWaitEvent failed");
     }
     h->stream = work;
     return rc;
@@ -1150,23 +1110,19 @@ static uint32_t* roff_take(kq_handle* h) {
     for (int i = 0; i < h->n_pend; ++i) if (h->pend_sets[i].n_max >> 32) return nullptr;      // offsets are stored in 32 bits
     const size_t need = roff_bytes(h->n_alloc_regions());
     if (!need || !roff_pitch((uint32_t)h->n_pend)) return nullptr;
-    if (h->roff.bytes < need) {
-        if (h->roff.p) { (void)hipFree(h->roff.p); h->roff = DevBuf(); }
-        if (hipMalloc(&h->roff.p, need) != hipSuccess) { (void)hipGetLastError(); h->roff.p = nullptr; return nullptr; }
-        h->roff.bytes = need;
-    }
-    return (uint32_t*)h->roff.p;
+    if (h->roff.bytes() < need && h->roff.alloc(need) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return h->roff.as<uint32_t>();
 }
 static int flush_pending_base(kq_handle* h) {
     const uint64_t R = h->n_regions;
-    int rc = ensure_buf(h->hot, (size_t)(R + 2) * 8);
-    if (rc) return rc;
+    HIPC(h->hot.ensure((size_t)(R + 2) * 8));
+    int rc;
     if (h->kmers_bound / 255 + 1 > (1ull << 23)) {       // large jobs: the side table follows its observed fill (see reserve)
         rc = read_state_raw(h); if (rc) return rc;
-        const uint64_t need_hc = std::max<uint64_t>(HC_CAP_BIG, 8 * h->st_host->hc_used);
+        const uint64_t need_hc = std::max<uint64_t>(HC_CAP_BIG, 8 * h->host_state()->hc_used);
         if (need_hc > h->hc_cap) { rc = grow_hc(h, need_hc); if (rc) return rc; }
     }
-    unsigned long long* hot = (unsigned long long*)h->hot.p;     // [0] = count, then up to R region ids
+    unsigned long long* hot = h->hot.as<unsigned long long>();     // [0] = count, then up to R region ids
     HIPC(hipMemsetAsync(hot, 0, 8, h->stream));
     const dim3 grid((unsigned)std::min<uint64_t>(h->n_alloc_regions(), 1u << 30)), grid_hot(h->n_cu), block(P3_THREADS);   // one workgroup per (allocated) region: dispatcher-balanced
     // 1: the slot array holds the empty image (skip reading it); 2: logically empty but not initialised (lazy kq_clear):
@@ -1174,9 +1130,9 @@ static int flush_pending_base(kq_handle* h) {
     const int empty = h->slots_dirty ? 2 : h->table_empty ? 1 : 0;
     const int fmt = h->pend_fmt;
     const uint32_t rps = (fmt == FMT_NARROW || fmt == FMT_TIGHT || fmt == FMT_TOP8) ? (uint32_t)(R >> NARROW_CBITS) : 1u;
-#define KQ_HOT(F) hipLaunchKernelGGL((k_count_regions<F, true>), grid_hot, block, 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps)
+#define KQ_HOT(F) hipLaunchKernelGGL((k_count_regions<F, true>), grid_hot, block, 0, h->stream, h->view(), h->d_sets.as<P3Set>(), (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps)
 #define KQ_P3(F) do { \
-        hipLaunchKernelGGL((k_count_regions<F, false>), grid, block, 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps); \
+        hipLaunchKernelGGL((k_count_regions<F, false>), grid, block, 0, h->stream, h->view(), h->d_sets.as<P3Set>(), (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps); \
         KQ_HOT(F); } while (0)
     // 4- and 5-byte records: the sets' region offsets are transposed first, the pass reads one row pair per region and adds the
     // regions' totals to TOT_LINES lines, which k_fold_totals adds to the table state behind it (KQ_OPT_KERNEL_SET bit 16, or no
@@ -1187,22 +1143,22 @@ static int flush_pending_base(kq_handle* h) {
             rows.pitch = roff_pitch((uint32_t)h->n_pend);
             if (!h->tot) {
                 const size_t tb = (size_t)TOT_LINES * 64;
-                if (hipMalloc((void**)&h->tot, tb) != hipSuccess) { (void)hipGetLastError(); h->tot = nullptr; }
-                else HIPC(hipMemsetAsync(h->tot, 0, tb, h->stream));
+                if (h->tot.alloc(tb) != hipSuccess) (void)hipGetLastError();
+                else HIPC(hipMemsetAsync(h->tot.get(), 0, tb, h->stream));
             }
-            rows.tot = h->tot;
+            rows.tot = h->tot.as<unsigned long long>();
             rows.roff = roff - h->reg_lo() * rows.pitch;                 // row r of the geometry (a window allocates its own rows only)
             for (int i = 0; i < h->n_pend; ++i) { rows.d[i].recs = (const uint32_t*)h->pend_sets[i].recs; rows.d[i].aux = h->pend_sets[i].aux; }
             const uint64_t n_rows = roff_rows(h->n_alloc_regions());
             hipLaunchKernelGGL(k_p3_region_offsets, dim3(grid_for(h, n_rows, ROFF_ROWS, 32)), dim3(ROFF_THREADS), 0, h->stream,
-                               roff, h->d_sets, (uint32_t)h->n_pend, rows.pitch, h->reg_lo(), n_rows);
+                               roff, h->d_sets.as<P3Set>(), (uint32_t)h->n_pend, rows.pitch, h->reg_lo(), n_rows);
         }
     }
 #define KQ_Q4(KC, T) do { \
         if (rows.roff) hipLaunchKernelGGL((k_count_regions_q4r<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), rows, empty, hot, rps); \
-        else hipLaunchKernelGGL((k_count_regions_q4<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), h->d_sets, (uint32_t)h->n_pend, empty, hot, rps); \
+        else hipLaunchKernelGGL((k_count_regions_q4<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), h->d_sets.as<P3Set>(), (uint32_t)h->n_pend, empty, hot, rps); \
         KQ_HOT(FMT_NARROW); \
-        if (rows.roff && rows.tot) hipLaunchKernelGGL(k_fold_totals, dim3(1), dim3(256), 0, h->stream, rows.tot, h->st); } while (0)
+        if (rows.roff && rows.tot) hipLaunchKernelGGL(k_fold_totals, dim3(1), dim3(256), 0, h->stream, rows.tot, h->d_state()); } while (0)
     // ordinary regions of 4- and 5-byte records: the compact 32-bit-key kernel; skewed ones: the generic folding kernel
     // (pend_aux_fmt == AUX_TIGHT tells it about FMT_TIGHT sets)
     if (fmt == FMT_TIGHT)       { if (h->k == 21) KQ_Q4(21, true); else KQ_Q4(0, true); }
@@ -1257,7 +1213,7 @@ static P3Set sort_to_regions(kq_handle* h, PartPlan* p, const LevelIn& in, const
         if (!arena && mid_to_2) { fin = p->recs1; fin_aux = p->a1(); }
         if (d.tight) fin_aux = nullptr;
         LevelCfg last = level_narrow(p->cfg, sb, false, t8);
-        if (d.tight) last.rstart = h->rstart;
+        if (d.tight) last.rstart = h->rstart.as<uint32_t>();
         if (sb == 0) {
             last.n_seg = in.n_seg; last.spb = in.spb;
             run_level(h, p, last, in, fin, fin_aux, fin_base);
@@ -1401,13 +1357,13 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
             slice = (kmers + n_slices - 1) / n_slices;           // equal slices
             size_t free_b = 0, total_b = 0;
             if (cap == (1ull << 30) || slice <= (1ull << 30)) break;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + h->work.part.bytes >= (size_t)11 * slice + ((size_t)2 << 30)) break;   // the plan takes ~10.2 B per start
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + h->work.part.bytes() >= (size_t)11 * slice + ((size_t)2 << 30)) break;   // the plan takes ~10.2 B per start
         }
     }
     if (h->pend_budget == 0 && !h->slice_user && kmers > slice && 2 * h->n_slots() > slice) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t by_mem = (uint64_t)((free_b + h->work.part.bytes) / 24);          // 16 B scratch + margin per start
+            const uint64_t by_mem = (uint64_t)((free_b + h->work.part.bytes()) / 24);          // 16 B scratch + margin per start
             slice = std::max(slice, std::min<uint64_t>(std::min<uint64_t>(2 * h->n_slots(), 1ull << 31), by_mem));
         }
     }
@@ -1424,10 +1380,10 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
     const bool forked = h->overlap && !h->profile && h->count_path != 1 && (kmers + slice - 1) / slice >= 2 && slice >= (1u << 20) &&
                         (h->overlap == 2 || (h->filt_lo == 0 && h->filt_hi == (uint32_t)h->map_count && !h->windowed));
     if (forked) {
-        for (int w = 0; w < 2; ++w) if (!h->fork_stream[w]) HIPC(hipStreamCreateWithFlags(&h->fork_stream[w], hipStreamNonBlocking));
+        for (int w = 0; w < 2; ++w) if (!h->fork_stream[w]) HIPC(h->fork_stream[w].create(hipStreamNonBlocking));
         hipEvent_t e_in; int erc = ev_get(h, &e_in); if (erc) return erc;
         HIPC(hipEventRecord(e_in, h->base));
-        for (int w = 0; w < 2; ++w) HIPC(hipStreamWaitEvent(h->fork_stream[w], e_in, 0));
+        for (int w = 0; w < 2; ++w) HIPC(hipStreamWaitEvent(h->fork_stream[w].get(), e_in, 0));
     }
     uint64_t slice_no = 0;
     for (uint64_t a = 0; a < kmers; a += slice, ++slice_no) {
@@ -1442,7 +1398,7 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
         double pass_records = (double)(b - a);
         if (h->pend_budget != 0) {
             const double per_set = (double)set_bytes(b - a, FMT_PACK8, h->n_regions).total;
-            const double room = h->arena ? (double)h->arena_bytes : 4.0 * (double)h->n_slots() * sizeof(Slot);
+            const double room = h->arena.p ? (double)h->arena_bytes : 4.0 * (double)h->n_slots() * sizeof(Slot);
             pass_records = (double)h->pend_records + (double)(b - a) * std::max(1.0, std::min(8.0, room / per_set));
         }
         bool part = (b - a) >= (1u << 20) && part_table_ok(h, true) &&
@@ -1456,7 +1412,7 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
             if (forked) {
                 const int w = (int)(slice_no & 1);
                 if (w == 1) { std::swap(h->work, h->fork_work); guard.swapped = true; }
-                h->stream = h->fork_stream[w];
+                h->stream = h->fork_stream[w].get();
                 h->fork_busy[w] = true;
             }
             rc = count_partitioned(h, v.ab, v.lead, v.len, v.er, v.pinv);
@@ -1527,24 +1483,23 @@ void kq_host_free(void* p) { if (p) { (void)hipHostUnregister(p); free(p); } }
 // A ticket and its staging slot (under h->in_m): the copy stream waits for the slot's previous reader, the slot holds `bytes`
 static int ingest_begin(kq_handle* h, size_t bytes, uint64_t* ticket, int* slot, hipEvent_t* copied) {
     if (!h->copy_stream) {
-        HIPC(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        for (int i = 0; i < kq_handle::IN_SLOTS; ++i) HIPC(hipEventCreateWithFlags(&h->in_consumed[i], hipEventDisableTiming));
+        // events first, the stream last: a failure on the way leaves no stream, and the next call starts over
+        for (auto& e : h->in_consumed) HIPC(e.create(hipEventDisableTiming));
         h->in_copied.resize(kq_handle::IN_TICKETS);
-        for (auto& e : h->in_copied) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto& e : h->in_copied) HIPC(e.create(hipEventDisableTiming));
+        HIPC(h->copy_stream.create(hipStreamNonBlocking));
     }
     const uint64_t t = h->in_next++;
     const int s = (int)(t % kq_handle::IN_SLOTS);
-    *copied = h->in_copied[t % kq_handle::IN_TICKETS];
+    *copied = h->in_copied[t % kq_handle::IN_TICKETS].get();
     *ticket = t; *slot = s;
     h->in_bad[t % kq_handle::IN_TICKETS] = 0;
     // the slot's previous reader must be done before it is overwritten (copy stream waits; the host does not)
-    if (t >= (uint64_t)kq_handle::IN_SLOTS) HIPC(hipStreamWaitEvent(h->copy_stream, h->in_consumed[s], 0));
-    if (h->in_buf[s].bytes < bytes + 64) {
+    if (t >= (uint64_t)kq_handle::IN_SLOTS) HIPC(hipStreamWaitEvent(h->copy_stream.get(), h->in_consumed[s].get(), 0));
+    if (h->in_buf[s].bytes() < bytes + 64) {
         // growing a slot: nothing may still read the old buffer
-        if (h->in_buf[s].p) { HIPC(hipStreamSynchronize(h->copy_stream)); HIPC(hipStreamSynchronize(h->stream)); HIPC(hipFree(h->in_buf[s].p)); h->in_buf[s] = DevBuf(); }
-        const size_t want = bytes + bytes / 4 + 4096;
-        HIPC(hipMalloc(&h->in_buf[s].p, want));
-        h->in_buf[s].bytes = want;
+        if (h->in_buf[s]) { HIPC(hipStreamSynchronize(h->copy_stream.get())); HIPC(hipStreamSynchronize(h->stream)); }
+        HIPC(h->in_buf[s].alloc(bytes + bytes / 4 + 4096));
     }
     return KQ_OK;
 }
@@ -1558,13 +1513,13 @@ static int ingest_async(kq_handle* h, const void* a, size_t a_bytes, const void*
     int s = 0; hipEvent_t copied;
     int rc = ingest_begin(h, bytes, ticket, &s, &copied);
     if (rc) return rc;
-    char* d = (char*)h->in_buf[s].p;
-    if (a_bytes) HIPC(hipMemcpyAsync(d, a, a_bytes, hipMemcpyHostToDevice, h->copy_stream));
-    if (b_bytes) HIPC(hipMemcpyAsync(d + b_off, b, b_bytes, hipMemcpyHostToDevice, h->copy_stream));
-    HIPC(hipEventRecord(copied, h->copy_stream));
+    char* d = h->in_buf[s].as<char>();
+    if (a_bytes) HIPC(hipMemcpyAsync(d, a, a_bytes, hipMemcpyHostToDevice, h->copy_stream.get()));
+    if (b_bytes) HIPC(hipMemcpyAsync(d + b_off, b, b_bytes, hipMemcpyHostToDevice, h->copy_stream.get()));
+    HIPC(hipEventRecord(copied, h->copy_stream.get()));
     HIPC(hipStreamWaitEvent(h->stream, copied, 0));
     rc = count_seq_dev(h, d, b ? (const uint16_t*)(d + b_off) : nullptr, n_bases);
-    HIPC(hipEventRecord(h->in_consumed[s], h->stream));
+    HIPC(hipEventRecord(h->in_consumed[s].get(), h->stream));
     return rc;
 }
 int kq_count_batch_async(kq_handle* h, const char* bases, uint64_t len, uint64_t* ticket) {
@@ -1581,7 +1536,7 @@ int kq_host_wait(kq_handle* h, uint64_t ticket) {
     if (!h) return fail(KQ_ERR_INVALID, "null handle");
     if (ticket >= h->in_next) return fail(KQ_ERR_INVALID, "unknown ticket %llu", (unsigned long long)ticket);
     if (h->in_next - ticket >= (uint64_t)kq_handle::IN_TICKETS) return KQ_OK;      // long recycled: that copy finished many batches ago
-    HIPC(hipEventSynchronize(h->in_copied[ticket % kq_handle::IN_TICKETS]));
+    HIPC(hipEventSynchronize(h->in_copied[ticket % kq_handle::IN_TICKETS].get()));
     if (const int bad = h->in_bad[ticket % kq_handle::IN_TICKETS])
         return fail(KQ_ERR_INVALID, "malformed %s text (ticket %llu): not counted", bad == KQ_FASTX_FASTQ ? "FASTQ" : "FASTA", (unsigned long long)ticket);
     return KQ_OK;
@@ -1607,9 +1562,10 @@ static int fx_args(kq_handle* h, const char* text, uint64_t len, int format) {
 }
 static uint64_t fx_units_of(const char* d_text, uint64_t len) { return (((uintptr_t)d_text & 15) + len + FX_UNIT - 1) / FX_UNIT; }
 static int fx_prepare(kq_handle* h, uint64_t n_units) {
-    if (!h->fx_res) HIPC(hipMalloc((void**)&h->fx_res, sizeof(FxResult)));
-    if (!h->fx_res_host) HIPC(hipHostMalloc((void**)&h->fx_res_host, sizeof(FxResult), hipHostMallocDefault));
-    return ensure_buf(h->fx_units, (size_t)n_units * sizeof(FxUnit));
+    if (!h->fx_res) HIPC(h->fx_res.alloc(sizeof(FxResult)));
+    if (!h->fx_res_host) HIPC(h->fx_res_host.alloc(sizeof(FxResult)));
+    HIPC(h->fx_units.ensure((size_t)n_units * sizeof(FxUnit)));
+    return KQ_OK;
 }
 // summaries + scan on `st` (len > 0): the units hold every unit's output offset and incoming state, fx_res the total
 static void fx_scan(kq_handle* h, hipStream_t st, const char* d_text, uint64_t len, int format) {
@@ -1617,13 +1573,13 @@ static void fx_scan(kq_handle* h, hipStream_t st, const char* d_text, uint64_t l
     aligned_view(d_text, &ab, &lead);
     const uint64_t n_units = fx_units_of(d_text, len);
     const dim3 grid((unsigned)((n_units + FX_THREADS / 64 - 1) / (FX_THREADS / 64)));
-    FxUnit* units = (FxUnit*)h->fx_units.p;
+    FxUnit* units = h->fx_units.as<FxUnit>();
     if (format == KQ_FASTX_FASTQ) {
         hipLaunchKernelGGL((k_fx_summary<FX_FASTQ>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, units);
-        hipLaunchKernelGGL((k_fx_scan<FX_FASTQ>), dim3(1), dim3(FX_SCAN_THREADS), 0, st, ab, lead, units, n_units, h->fx_res);
+        hipLaunchKernelGGL((k_fx_scan<FX_FASTQ>), dim3(1), dim3(FX_SCAN_THREADS), 0, st, ab, lead, units, n_units, h->fx_res.as<FxResult>());
     } else {
         hipLaunchKernelGGL((k_fx_summary<FX_FASTA>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, units);
-        hipLaunchKernelGGL((k_fx_scan<FX_FASTA>), dim3(1), dim3(FX_SCAN_THREADS), 0, st, ab, lead, units, n_units, h->fx_res);
+        hipLaunchKernelGGL((k_fx_scan<FX_FASTA>), dim3(1), dim3(FX_SCAN_THREADS), 0, st, ab, lead, units, n_units, h->fx_res.as<FxResult>());
     }
 }
 // kept bytes -> d_out (nullptr: the record checks only)
@@ -1632,12 +1588,12 @@ static void fx_apply(kq_handle* h, hipStream_t st, const char* d_text, uint64_t 
     aligned_view(d_text, &ab, &lead);
     const uint64_t n_units = fx_units_of(d_text, len);
     const dim3 grid((unsigned)((n_units + FX_THREADS / 64 - 1) / (FX_THREADS / 64)));
-    if (format == KQ_FASTX_FASTQ) hipLaunchKernelGGL((k_fx_apply<FX_FASTQ>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, (const FxUnit*)h->fx_units.p, (uint8_t*)d_out, h->fx_res);
-    else hipLaunchKernelGGL((k_fx_apply<FX_FASTA>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, (const FxUnit*)h->fx_units.p, (uint8_t*)d_out, h->fx_res);
+    if (format == KQ_FASTX_FASTQ) hipLaunchKernelGGL((k_fx_apply<FX_FASTQ>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, h->fx_units.as<const FxUnit>(), (uint8_t*)d_out, h->fx_res.as<FxResult>());
+    else hipLaunchKernelGGL((k_fx_apply<FX_FASTA>), grid, dim3(FX_THREADS), 0, st, ab, lead, lead + len, n_units, h->fx_units.as<const FxUnit>(), (uint8_t*)d_out, h->fx_res.as<FxResult>());
 }
 static int fx_read_result(kq_handle* h, hipStream_t st) {
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(h->fx_res_host, h->fx_res, sizeof(FxResult), hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(h->fx_res_host.get(), h->fx_res.get(), sizeof(FxResult), hipMemcpyDeviceToHost, st));
     HIPC(hipStreamSynchronize(st));
     return KQ_OK;
 }
@@ -1656,12 +1612,12 @@ int kq_parse_fastx_dev(kq_handle* h, const char* d_text, uint64_t len, int forma
     rc = fx_prepare(h, fx_units_of(d_text, len)); if (rc) return rc;
     fx_scan(h, h->stream, d_text, len, format);
     rc = fx_read_result(h, h->stream); if (rc) return rc;
-    const uint64_t n = h->fx_res_host->n_bases;
+    const uint64_t n = h->fx_host()->n_bases;
     *n_bases = n;
     const bool fits = d_bases && n <= cap;
     fx_apply(h, h->stream, d_text, len, format, fits ? d_bases : nullptr);
     rc = fx_read_result(h, h->stream); if (rc) return rc;
-    if (h->fx_res_host->bad) return fail(KQ_ERR_INVALID, "malformed %s text (%s)", fx_name(format), fx_rule(format));
+    if (h->fx_host()->bad) return fail(KQ_ERR_INVALID, "malformed %s text (%s)", fx_name(format), fx_rule(format));
     if (d_bases && !fits) return fail(KQ_ERR_CAPACITY, "output buffer too small: %llu bases, room for %llu", (unsigned long long)n, (unsigned long long)cap);
     return KQ_OK;
 }
@@ -1675,17 +1631,17 @@ int kq_count_fastx_dev(kq_handle* h, const char* d_text, uint64_t len, int forma
     if (!len) return KQ_OK;
     HIPC(hipSetDevice(h->device));
     rc = fx_prepare(h, fx_units_of(d_text, len)); if (rc) return rc;
-    if (h->fx_out.bytes < len + 64) {
+    if (h->fx_out.bytes() < len + 64) {
         HIPC(hipStreamSynchronize(h->stream));             // (an earlier count may still read the old buffer)
-        rc = ensure_buf(h->fx_out, len + 64); if (rc) return rc;
+        HIPC(h->fx_out.ensure(len + 64));
     }
     fx_scan(h, h->stream, d_text, len, format);
-    fx_apply(h, h->stream, d_text, len, format, (char*)h->fx_out.p);
+    fx_apply(h, h->stream, d_text, len, format, h->fx_out.as<char>());
     // the count path plans its slices and scratch from the batch size on the host: one 16-byte read per call
     rc = fx_read_result(h, h->stream); if (rc) return rc;
-    if (h->fx_res_host->bad) { h->fx_bad = format; return KQ_OK; }       // not counted; kq_sync reports it
+    if (h->fx_host()->bad) { h->fx_bad = format; return KQ_OK; }       // not counted; kq_sync reports it
     HistCacheOff guard(h);
-    return count_seq_dev(h, (const char*)h->fx_out.p, nullptr, h->fx_res_host->n_bases);
+    return count_seq_dev(h, h->fx_out.as<const char>(), nullptr, h->fx_host()->n_bases);
 }
 
 int kq_count_fastx_async(kq_handle* h, const char* text, uint64_t len, int format, uint64_t* ticket) {
@@ -1697,28 +1653,28 @@ int kq_count_fastx_async(kq_handle* h, const char* text, uint64_t len, int forma
     std::lock_guard<std::mutex> lock(h->in_m);
     int s = 0; hipEvent_t copied;
     rc = ingest_begin(h, len, ticket, &s, &copied); if (rc) return rc;
-    if (h->in_cmp[s].bytes < len + 64) {
-        if (h->in_cmp[s].p) { HIPC(hipStreamSynchronize(h->copy_stream)); HIPC(hipStreamSynchronize(h->stream)); }
-        rc = ensure_buf(h->in_cmp[s], len + 64); if (rc) return rc;
+    if (h->in_cmp[s].bytes() < len + 64) {
+        if (h->in_cmp[s]) { HIPC(hipStreamSynchronize(h->copy_stream.get())); HIPC(hipStreamSynchronize(h->stream)); }
+        HIPC(h->in_cmp[s].ensure(len + 64));
     }
-    rc = fx_prepare(h, fx_units_of((const char*)h->in_buf[s].p, len)); if (rc) return rc;
+    rc = fx_prepare(h, fx_units_of(h->in_buf[s].as<const char>(), len)); if (rc) return rc;
     // copy and parse on the copy stream: beside the counting of earlier batches.  The call waits for ITS OWN copy and parse
     // (the batch size plans the count on the host), never for the counting of earlier batches unless the ring is full
-    char* d = (char*)h->in_buf[s].p;
-    HIPC(hipMemcpyAsync(d, text, len, hipMemcpyHostToDevice, h->copy_stream));
-    HIPC(hipEventRecord(copied, h->copy_stream));
-    fx_scan(h, h->copy_stream, d, len, format);
-    fx_apply(h, h->copy_stream, d, len, format, (char*)h->in_cmp[s].p);
-    rc = fx_read_result(h, h->copy_stream); if (rc) return rc;
-    if (h->fx_res_host->bad) {
+    char* d = h->in_buf[s].as<char>();
+    HIPC(hipMemcpyAsync(d, text, len, hipMemcpyHostToDevice, h->copy_stream.get()));
+    HIPC(hipEventRecord(copied, h->copy_stream.get()));
+    fx_scan(h, h->copy_stream.get(), d, len, format);
+    fx_apply(h, h->copy_stream.get(), d, len, format, h->in_cmp[s].as<char>());
+    rc = fx_read_result(h, h->copy_stream.get()); if (rc) return rc;
+    if (h->fx_host()->bad) {
         h->in_bad[*ticket % kq_handle::IN_TICKETS] = (uint8_t)format;
         h->fx_bad = format;
         rc = KQ_OK;
     } else {
         HistCacheOff guard(h);
-        rc = count_seq_dev(h, (const char*)h->in_cmp[s].p, nullptr, h->fx_res_host->n_bases);
+        rc = count_seq_dev(h, h->in_cmp[s].as<const char>(), nullptr, h->fx_host()->n_bases);
     }
-    HIPC(hipEventRecord(h->in_consumed[s], h->stream));
+    HIPC(hipEventRecord(h->in_consumed[s].get(), h->stream));
     return rc;
 }
 
@@ -1727,9 +1683,8 @@ static int emit_ordered(kq_handle* h, const char* d_bases, uint64_t len, uint64_
     const uint8_t* ab; uint64_t lead;
     aligned_view(d_bases, &ab, &lead);
     const uint64_t nt = n_tiles_of(lead, len);
-    int rc = ensure_buf(h->scratch, (nt + 2) * sizeof(unsigned long long));
-    if (rc) return rc;
-    unsigned long long* tile_counts = (unsigned long long*)h->scratch.p;
+    HIPC(h->scratch.ensure((nt + 2) * sizeof(unsigned long long)));
+    unsigned long long* tile_counts = h->scratch.as<unsigned long long>();
     unsigned long long* total = tile_counts + nt;
     int grid = grid_for(h, nt, 1);
     hipLaunchKernelGGL(k_emit_count, dim3(grid), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, tile_counts);
@@ -1758,10 +1713,11 @@ int kq_emit_records(kq_handle* h, const char* bases, uint64_t len, uint64_t* key
     if (rc) return rc;
     if (*n_out > cap) return fail(KQ_ERR_CAPACITY, "record buffer too small: need %llu, have %llu", (unsigned long long)*n_out, (unsigned long long)cap);
     uint64_t n = *n_out;
+    DevScope mem;
     uint64_t* dk = nullptr; uint8_t* de = nullptr;
     if (n) {
-        HIPC(hipMalloc((void**)&dk, n * sizeof(uint64_t)));
-        if (hipMalloc((void**)&de, n) != hipSuccess) { (void)hipFree(dk); return fail(KQ_ERR_NOMEM, "record buffer allocation failed"); }
+        HIPC(mem.alloc((void**)&dk, n * sizeof(uint64_t)));
+        if (mem.alloc((void**)&de, n) != hipSuccess) return fail(KQ_ERR_NOMEM, "record buffer allocation failed");
         rc = emit_ordered(h, (const char*)d, len, dk, de, n, n_out);
         if (!rc) {
             hipError_t e1 = hipMemcpyAsync(keys, dk, n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream);
@@ -1769,7 +1725,6 @@ int kq_emit_records(kq_handle* h, const char* bases, uint64_t len, uint64_t* key
             hipError_t e3 = hipStreamSynchronize(h->stream);
             if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc = fail(KQ_ERR_HIP, "copying records back failed");
         }
-        (void)hipFree(dk); (void)hipFree(de);
     }
     return rc;
 }
@@ -1897,9 +1852,8 @@ int kq_insert_sharded_dev(kq_handle* h, const uint32_t* d_recs, const uint8_t* d
     if (rc) return rc;
     if (p.fmt != FMT_NARROW) return fail(KQ_ERR_INVALID, "the table is too small for 5-byte records (fewer than 2048 regions): use kq_insert_packed_dev");
     // segment table of the received array (peer-major runs) in logical order (bucket-major)
-    rc = ensure_buf(h->scratch, (size_t)(3 * (n_in + 2)) * 8);
-    if (rc) return rc;
-    unsigned long long* start = (unsigned long long*)h->scratch.p;
+    HIPC(h->scratch.ensure((size_t)(3 * (n_in + 2)) * 8));
+    unsigned long long* start = h->scratch.as<unsigned long long>();
     unsigned long long* seg_lo = start + n_in + 2;
     unsigned long long* seg_hi = seg_lo + n_in + 2;
     HIPC(hipMemcpyAsync(start, d_bucket_counts, (size_t)n_in * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -1968,9 +1922,8 @@ int kq_insert_sharded8_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n, int
     if (rc) return rc;
     if (p.fmt != FMT_TOP8) return fail(KQ_ERR_INVALID, "the table has no hash-prefix bucket split for 8-byte hash-remainder records: use kq_insert_records_dev");
     // segment table of the received array (peer-major runs) in logical order (bucket-major)
-    rc = ensure_buf(h->scratch, (size_t)(3 * (n_in + 2)) * 8);
-    if (rc) return rc;
-    unsigned long long* start = (unsigned long long*)h->scratch.p;
+    HIPC(h->scratch.ensure((size_t)(3 * (n_in + 2)) * 8));
+    unsigned long long* start = h->scratch.as<unsigned long long>();
     unsigned long long* seg_lo = start + n_in + 2;
     unsigned long long* seg_hi = seg_lo + n_in + 2;
     HIPC(hipMemcpyAsync(start, d_bucket_counts, (size_t)n_in * 8, hipMemcpyDeviceToDevice, h->stream));
@@ -2014,13 +1967,12 @@ int kq_insert_records(kq_handle* h, const uint64_t* keys, const uint8_t* edges, 
     if (!h || ((!keys || !edges) && n)) return fail(KQ_ERR_INVALID, "null argument");
     HIPC(hipSetDevice(h->device));
     if (!n) return KQ_OK;
-    int rc = ensure_buf(h->stage, n * 9 + 64);
-    if (rc) return rc;
-    uint64_t* dk = (uint64_t*)h->stage.p;
-    uint8_t* de = (uint8_t*)h->stage.p + n * 8;
+    HIPC(h->stage.ensure(n * 9 + 64));
+    uint64_t* dk = h->stage.as<uint64_t>();
+    uint8_t* de = h->stage.as<uint8_t>() + n * 8;
     HIPC(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, h->stream));
     HIPC(hipMemcpyAsync(de, edges, n, hipMemcpyHostToDevice, h->stream));
-    rc = kq_insert_records_dev(h, dk, de, n);
+    int rc = kq_insert_records_dev(h, dk, de, n);
     if (rc) return rc;
     return kq_sync(h);
 }
@@ -2030,12 +1982,11 @@ struct SummaryHost { SummaryOut so; std::vector<unsigned long long> small; std::
 static int run_summary(kq_handle* h, SummaryHost* r) {
     const uint64_t big_cap = h->hc_cap;     // cov >= 4096 implies a high-copy k-mer
     size_t need = sizeof(SummaryOut) + HIST_SMALL * sizeof(unsigned long long) + big_cap * sizeof(uint32_t);
-    int rc = ensure_buf(h->scratch, need);
-    if (rc) return rc;
-    SummaryOut* d_so = (SummaryOut*)h->scratch.p;
+    HIPC(h->scratch.ensure(need));
+    SummaryOut* d_so = h->scratch.as<SummaryOut>();
     unsigned long long* d_small = (unsigned long long*)(d_so + 1);
     uint32_t* d_big = (uint32_t*)(d_small + HIST_SMALL);
-    HIPC(hipMemsetAsync(h->scratch.p, 0, sizeof(SummaryOut) + HIST_SMALL * sizeof(unsigned long long), h->stream));
+    HIPC(hipMemsetAsync(h->scratch.get(), 0, sizeof(SummaryOut) + HIST_SMALL * sizeof(unsigned long long), h->stream));
     SummaryOut init; memset(&init, 0, sizeof init); init.big_cap = big_cap;
     HIPC(hipMemcpyAsync(d_so, &init, sizeof init, hipMemcpyHostToDevice, h->stream));
     materialize(h);
@@ -2148,12 +2099,13 @@ int kq_lookup_sequence(kq_handle* h, const char* bases, uint64_t len, uint32_t c
     void* d = nullptr;
     rc = stage_in(h, bases, len, &d);
     if (rc) return rc;
+    DevScope mem;
     unsigned long long* d_ctr = nullptr;
     kq_dbgbase* d_pb = nullptr;
-    HIPC(hipMalloc((void**)&d_ctr, 3 * sizeof(unsigned long long)));
+    HIPC(mem.alloc((void**)&d_ctr, 3 * sizeof(unsigned long long)));
     (void)hipMemsetAsync(d_ctr, 0, 3 * sizeof(unsigned long long), h->stream);
     if (per_base && len) {
-        if (hipMalloc((void**)&d_pb, len * sizeof(kq_dbgbase)) != hipSuccess) { (void)hipFree(d_ctr); return fail(KQ_ERR_NOMEM, "per-base buffer allocation failed"); }
+        if (mem.alloc((void**)&d_pb, len * sizeof(kq_dbgbase)) != hipSuccess) return fail(KQ_ERR_NOMEM, "per-base buffer allocation failed");
         (void)hipMemcpyAsync(d_pb, per_base, len * sizeof(kq_dbgbase), hipMemcpyHostToDevice, h->stream);
     }
     rc = kq_lookup_sequence_dev(h, (const char*)d, len, cov_cutoff, map_lo, map_hi, d_pb, (uint64_t*)d_ctr);
@@ -2164,8 +2116,6 @@ int kq_lookup_sequence(kq_handle* h, const char* bases, uint64_t len, uint32_t c
         hipError_t e3 = hipStreamSynchronize(h->stream);
         if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) rc = fail(KQ_ERR_HIP, "lookup failed: %s", hipGetErrorString(e3));
     }
-    (void)hipFree(d_ctr);
-    if (d_pb) (void)hipFree(d_pb);
     if (!rc) for (int i = 0; i < 3; ++i) counters[i] += c[i];
     return rc;
 }
@@ -2179,9 +2129,8 @@ int kq_lookup_keys(kq_handle* h, const uint64_t* keys, uint64_t n, kq_entry* out
     if (rc) return rc;
     materialize(h);
     // keys in, entries out: one scratch buffer (8 + 48 bytes per key)
-    rc = ensure_buf(h->stage, (size_t)n * (sizeof(uint64_t) + sizeof(kq_entry)) + 64);
-    if (rc) return rc;
-    uint64_t* d_keys = (uint64_t*)h->stage.p;
+    HIPC(h->stage.ensure((size_t)n * (sizeof(uint64_t) + sizeof(kq_entry)) + 64));
+    uint64_t* d_keys = h->stage.as<uint64_t>();
     kq_entry* d_out = (kq_entry*)(d_keys + ((n + 1) & ~1ull));
     HIPC(hipMemcpyAsync(d_keys, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_lookup_keys, dim3(grid_for(h, n, 256)), dim3(256), 0, h->stream, h->view(), d_keys, n, d_out);
@@ -2200,8 +2149,9 @@ int kq_branch_scan(kq_handle* h, const char* bases, uint64_t len, uint32_t cov_c
     void* d = nullptr;
     rc = stage_in(h, bases, len, &d);
     if (rc) return rc;
+    DevScope mem;
     uint8_t* d_flags = nullptr;
-    HIPC(hipMalloc((void**)&d_flags, len));
+    HIPC(mem.alloc((void**)&d_flags, len));
     (void)hipMemsetAsync(d_flags, 0, len, h->stream);
     const uint8_t* ab; uint64_t lead;
     aligned_view((const char*)d, &ab, &lead);
@@ -2209,7 +2159,6 @@ int kq_branch_scan(kq_handle* h, const char* bases, uint64_t len, uint32_t cov_c
                        cov_cutoff, d_flags);
     hipError_t e1 = hipMemcpyAsync(flags, d_flags, len, hipMemcpyDeviceToHost, h->stream);
     hipError_t e2 = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_flags);
     if (e1 != hipSuccess || e2 != hipSuccess) return fail(KQ_ERR_HIP, "branch scan failed: %s", hipGetErrorString(e2 != hipSuccess ? e2 : e1));
     return KQ_OK;
 }
@@ -2228,10 +2177,10 @@ int kq_merge(kq_handle* dst, kq_handle* src) {
     if (rc) return rc;
     rc = read_state(src);
     if (rc) return rc;
-    rc = reserve(dst, src->st_host->slots_used, src->st_host->kmers_added);
+    rc = reserve(dst, src->host_state()->slots_used, src->host_state()->kmers_added);
     if (rc) return rc;
     // enough source entries to pay for streaming dst once: merge region by region in LDS; else per-entry atomics
-    if (dst->merge_path == 2 || (dst->merge_path == 0 && src->st_host->slots_used * 64 >= dst->n_slots())) {
+    if (dst->merge_path == 2 || (dst->merge_path == 0 && src->host_state()->slots_used * 64 >= dst->n_slots())) {
         const int empty = (dst->table_empty || dst->slots_dirty) ? 1 : 0;     // a dirty (lazily cleared) array is never read
         hipLaunchKernelGGL(k_merge_regions, dim3((unsigned)std::min<uint64_t>(dst->n_alloc_regions(), 1u << 30)), dim3(P3_THREADS), 0, dst->stream,
                            dst->view(), src->view(), empty);
@@ -2272,16 +2221,16 @@ int kq_import(kq_handle* h, const kq_entry* entries, uint64_t n) {
     return kq_sync(h);
 }
 
-// key order on the device: radix sort of (key, index) + gather into a fresh array (*d_sorted, the caller frees it).  false, and
-// nothing kept, when there is no memory for it (or n >= 2^32)
-static bool sort_entries_dev(kq_handle* h, const kq_entry* d_in, uint64_t n, kq_entry** d_sorted_out) {
+// key order on the device: radix sort of (key, index) + gather into a fresh array (*d_sorted, which stays in the caller's `mem`;
+// the temporaries are released before the return).  false, and nothing kept, when there is no memory for it (or n >= 2^32)
+static bool sort_entries_dev(kq_handle* h, DevScope& mem, const kq_entry* d_in, uint64_t n, kq_entry** d_sorted_out) {
     kq_entry* d_sorted = nullptr; uint64_t *d_k1 = nullptr, *d_k2 = nullptr; uint32_t *d_i1 = nullptr, *d_i2 = nullptr; void* d_tmp = nullptr;
     size_t tmp_bytes = 0;
     bool on_device = n < (1ull << 32) &&
         hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_k1, d_k2, d_i1, d_i2, (int64_t)n, 0, 2 * h->k, h->stream) == hipSuccess &&
-        hipMalloc((void**)&d_sorted, n * sizeof(kq_entry)) == hipSuccess && hipMalloc((void**)&d_k1, n * 8) == hipSuccess &&
-        hipMalloc((void**)&d_k2, n * 8) == hipSuccess && hipMalloc((void**)&d_i1, n * 4) == hipSuccess &&
-        hipMalloc((void**)&d_i2, n * 4) == hipSuccess && hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8) == hipSuccess;
+        mem.alloc((void**)&d_sorted, n * sizeof(kq_entry)) == hipSuccess && mem.alloc((void**)&d_k1, n * 8) == hipSuccess &&
+        mem.alloc((void**)&d_k2, n * 8) == hipSuccess && mem.alloc((void**)&d_i1, n * 4) == hipSuccess &&
+        mem.alloc((void**)&d_i2, n * 4) == hipSuccess && mem.alloc(&d_tmp, tmp_bytes) == hipSuccess;
     if (on_device) {
         hipLaunchKernelGGL(k_entry_keys, dim3(grid_for(h, n, 256)), dim3(256), 0, h->stream, d_in, n, d_k1, d_i1);
         on_device = hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k1, d_k2, d_i1, d_i2, (int64_t)n, 0, 2 * h->k, h->stream) == hipSuccess;
@@ -2291,7 +2240,7 @@ static bool sort_entries_dev(kq_handle* h, const kq_entry* d_in, uint64_t n, kq_
         }
     }
     if (!on_device) (void)hipGetLastError();
-    for (void* q : {(void*)d_k1, (void*)d_k2, (void*)d_i1, (void*)d_i2, d_tmp, on_device ? nullptr : (void*)d_sorted}) if (q) (void)hipFree(q);
+    for (void* q : {(void*)d_k1, (void*)d_k2, (void*)d_i1, (void*)d_i2, d_tmp, on_device ? nullptr : (void*)d_sorted}) mem.release(q);
     *d_sorted_out = on_device ? d_sorted : nullptr;
     return on_device;
 }
@@ -2299,24 +2248,23 @@ static bool sort_entries_dev(kq_handle* h, const kq_entry* d_in, uint64_t n, kq_
 // rate: 0.25 s for 850 MB); the DMA of chunk i+1 overlaps the host copy of chunk i
 static hipError_t copy_out_bounced(kq_handle* h, void* out, const void* src, size_t bytes) {
     const size_t chunk = (size_t)16 << 20;
-    void* bounce[2] = {nullptr, nullptr};
+    PinnedMem bounce[2];
     hipError_t e;
-    if (bytes > 4 * chunk && hipHostMalloc(&bounce[0], chunk, hipHostMallocDefault) == hipSuccess && hipHostMalloc(&bounce[1], chunk, hipHostMallocDefault) == hipSuccess) {
+    if (bytes > 4 * chunk && bounce[0].alloc(chunk) == hipSuccess && bounce[1].alloc(chunk) == hipSuccess) {
         const size_t n_chunks = (bytes + chunk - 1) / chunk;
         auto len_of = [&](size_t c) { return std::min(chunk, bytes - c * chunk); };
-        e = hipMemcpyAsync(bounce[0], (const char*)src, len_of(0), hipMemcpyDeviceToHost, h->stream);
+        e = hipMemcpyAsync(bounce[0].get(), (const char*)src, len_of(0), hipMemcpyDeviceToHost, h->stream);
         for (size_t c = 0; c < n_chunks && e == hipSuccess; ++c) {
             e = hipStreamSynchronize(h->stream);
             if (e == hipSuccess && c + 1 < n_chunks)
-                e = hipMemcpyAsync(bounce[(c + 1) & 1], (const char*)src + (c + 1) * chunk, len_of(c + 1), hipMemcpyDeviceToHost, h->stream);
-            memcpy((char*)out + c * chunk, bounce[c & 1], len_of(c));
+                e = hipMemcpyAsync(bounce[(c + 1) & 1].get(), (const char*)src + (c + 1) * chunk, len_of(c + 1), hipMemcpyDeviceToHost, h->stream);
+            memcpy((char*)out + c * chunk, bounce[c & 1].get(), len_of(c));
         }
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     } else {
         (void)hipGetLastError();
         e = hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost);
     }
-    for (void* b : bounce) if (b) (void)hipHostFree(b);
     return e;
 }
 
@@ -2326,12 +2274,13 @@ int kq_export(kq_handle* h, uint16_t map_lo, uint16_t map_hi, kq_entry* out, uin
     HIPC(hipSetDevice(h->device));
     int rc = check_errors(h);
     if (rc) return rc;
+    DevScope mem;
     unsigned long long* d_n = nullptr;
     kq_entry* d_out = nullptr;
-    HIPC(hipMalloc((void**)&d_n, sizeof(unsigned long long)));
+    HIPC(mem.alloc((void**)&d_n, sizeof(unsigned long long)));
     (void)hipMemsetAsync(d_n, 0, sizeof(unsigned long long), h->stream);
     if (out && cap) {
-        if (hipMalloc((void**)&d_out, cap * sizeof(kq_entry)) != hipSuccess) { (void)hipFree(d_n); return fail(KQ_ERR_NOMEM, "export buffer allocation failed"); }
+        if (mem.alloc((void**)&d_out, cap * sizeof(kq_entry)) != hipSuccess) return fail(KQ_ERR_NOMEM, "export buffer allocation failed");
     }
     materialize(h);
     hipLaunchKernelGGL(k_export, dim3(grid_for(h, h->n_slots(), 1024)), dim3(256), 0, h->stream, h->view(), (uint32_t)h->map_count,
@@ -2346,33 +2295,16 @@ int kq_export(kq_handle* h, uint16_t map_lo, uint16_t map_hi, kq_entry* out, uin
         else if (n) {
             // key order on the device when there is memory for it, else on the host
             kq_entry* d_sorted = nullptr;
-            const bool on_device = sort_entries_dev(h, d_out, n, &d_sorted);
+            const bool on_device = sort_entries_dev(h, mem, d_out, n, &d_sorted);
             e = copy_out_bounced(h, out, on_device ? d_sorted : d_out, (size_t)n * sizeof(kq_entry));
             if (e != hipSuccess) rc = fail(KQ_ERR_HIP, "export copy failed: %s", hipGetErrorString(e));
             else if (!on_device) parallel_sort_entries(out, n);
-            if (d_sorted) (void)hipFree(d_sorted);
         }
     }
-    (void)hipFree(d_n);
-    if (d_out) (void)hipFree(d_out);
     return rc;
 }
 
 // ---- database map files as device-built / device-parsed images (kq_dbimage.h) -----------------------------------------
-namespace {
-struct DevPtrs {                       // device allocations of one call, freed on every way out
-    std::vector<void*> v;
-    ~DevPtrs() { for (void* p : v) if (p) (void)hipFree(p); }
-    hipError_t alloc(void** p, size_t bytes) {
-        *p = nullptr;
-        hipError_t e = hipMalloc(p, bytes ? bytes : 8);
-        if (e == hipSuccess) v.push_back(*p); else (void)hipGetLastError();
-        return e;
-    }
-    void release(void* p) { for (void*& q : v) if (q == p) { (void)hipFree(q); q = nullptr; } }
-};
-}  // namespace
-
 int kq_export_map_images(kq_handle* h, uint16_t map_lo, uint16_t map_hi, void* out, uint64_t cap, uint64_t* offsets,
                          kq_entry* hc_out, uint64_t hc_cap, uint64_t* n_hc) {
     if (!offsets || !n_hc) return fail(KQ_ERR_INVALID, "null offsets / n_hc");
@@ -2386,7 +2318,7 @@ int kq_export_map_images(kq_handle* h, uint16_t map_lo, uint16_t map_hi, void* o
     int rc = check_errors(h);          // flushes pending records
     if (rc) return rc;
     materialize(h);
-    DevPtrs mem;
+    DevScope mem;
     // sizes: k-mers per (map, submap) + the high-copy count
     unsigned long long* d_cnt = nullptr;
     HIPC(mem.alloc((void**)&d_cnt, (size_t)(n_sub + 1) * 8));
@@ -2423,8 +2355,7 @@ int kq_export_map_images(kq_handle* h, uint16_t map_lo, uint16_t map_hi, void* o
         hipLaunchKernelGGL(k_export, dim3(grid_for(h, h->n_slots(), 1024)), dim3(256), 0, h->stream, h->view(), (uint32_t)h->map_count,
                            (uint32_t)map_lo, (uint32_t)map_hi, d_ent, n, d_n);
         HIPC(hipGetLastError());
-        if (!sort_entries_dev(h, d_ent, n, &d_sorted)) return fail(KQ_ERR_NOMEM, "no device memory to sort the %llu entries of maps [%u,%u)", (unsigned long long)n, map_lo, map_hi);
-        mem.v.push_back(d_sorted);
+        if (!sort_entries_dev(h, mem, d_ent, n, &d_sorted)) return fail(KQ_ERR_NOMEM, "no device memory to sort the %llu entries of maps [%u,%u)", (unsigned long long)n, map_lo, map_hi);
         mem.release(d_ent);
         // records + stable split by (map, submap), least significant digit first
         const uint32_t G = (uint32_t)std::min<uint64_t>(1024, (n + 255) / 256);
@@ -2468,7 +2399,7 @@ int kq_import_map_image(kq_handle* h, uint16_t map, const void* image, uint64_t 
     if (map >= h->map_count) return fail(KQ_ERR_INVALID, "map %u outside [0,%d)", map, h->map_count);
     if (!total) return KQ_OK;                               // 6152 bytes: an empty map
     HIPC(hipSetDevice(h->device));
-    DevPtrs mem;
+    DevScope mem;
     uint8_t* d_img = nullptr; DbiExtent* d_ext = nullptr; DbiCheck* d_res = nullptr;
     if (mem.alloc((void**)&d_img, (size_t)n_bytes) != hipSuccess || mem.alloc((void**)&d_ext, ext.size() * sizeof(DbiExtent)) != hipSuccess || mem.alloc((void**)&d_res, sizeof(DbiCheck)) != hipSuccess)
         return fail(KQ_ERR_NOMEM, "no device memory for a map image of %llu bytes", (unsigned long long)n_bytes);
@@ -2530,7 +2461,7 @@ int kq_subgraph_seed_dev(kq_handle* db, kq_handle* sub, const char* d_bases, uin
     if (len < (uint64_t)k) return KQ_OK;
     hipStream_t st = sub->stream;
     const uint64_t n_pos = len - (uint64_t)k + 1, set_size = pow2_at_least(2 * n_pos);
-    DevPtrs mem;
+    DevScope mem;
     uint32_t *d_flag = nullptr, *d_seg = nullptr, *d_set = nullptr;
     uint64_t* d_key = nullptr; uint8_t* d_info = nullptr; void* d_tmp = nullptr;
     struct Res { SgSeedOut out; unsigned int err, pad; } res;
@@ -2583,7 +2514,7 @@ namespace {
 // The found list of an expansion -- ents[0, n_seed) = the seed k-mers with their subgraph entries, ents[n_seed, n_ents) = what
 // was found, in the order found -- and the visited key set (load <= 1/2) of the k-mers found.  Both double like a table.
 struct SgFound {
-    DevPtrs mem;
+    DevScope mem;
     SgExpandState* d_state = nullptr;
     kq_entry* d_ents = nullptr; uint64_t* d_vis = nullptr;
     uint64_t ents_cap = 0, vis_size = 0;
@@ -2626,11 +2557,11 @@ int kq_subgraph_expand(kq_handle* db, kq_handle* sub, int depth, uint64_t* n_add
     if (rc) return rc;
     rc = check_errors(sub);
     if (rc) return rc;
-    const uint64_t n_seed = sub->st_host->slots_used;
+    const uint64_t n_seed = sub->host_state()->slots_used;
     if (!depth || !n_seed) return KQ_OK;
     hipStream_t st = sub->stream;
     SgFound fl;
-    DevPtrs& mem = fl.mem;
+    DevScope& mem = fl.mem;
     SgExpandState state{};
     SgExpandState*& d_state = fl.d_state;
     kq_entry*& d_ents = fl.d_ents; uint64_t*& d_vis = fl.d_vis;
@@ -2688,7 +2619,7 @@ int kq_subgraph_best_first(kq_handle* db, kq_handle* sub, int depth, uint32_t co
     if (rc) return rc;
     rc = check_errors(sub);
     if (rc) return rc;
-    const uint64_t n_seed = sub->st_host->slots_used;
+    const uint64_t n_seed = sub->host_state()->slots_used;
     if (!depth || !n_seed) return KQ_OK;             // depth 0: the one pop meets seeds or inserts nodes, and nothing lies between a destination and its source
     hipStream_t st = sub->stream;
     SgFound fl;
