@@ -23,6 +23,7 @@
 #include "kq_mem_host.h"
 #include "kq_roff_host.h"
 #include "kq_seg_gate_host.h"
+#include "kq_select_host.h"
 
 using namespace kq;
 
@@ -439,6 +440,27 @@ static void parallel_sort_entries(kq_entry* a, uint64_t n) {
     }
 }
 
+// ---- kernel rows: a row pairs a descriptor of the selector (kq_select_host.h) with the instantiation it names.  The launchers
+// below list the rows of each family once; launch_row runs the row equal to `s`, and a descriptor that no row has is an error,
+// never another kernel
+template <class Fn> struct KernelRow { KernelSel sel; Fn fn; };
+template <class Fn, size_t N, class... A>
+static int launch_row(const KernelRow<Fn> (&rows)[N], const char* family, const KernelSel& s, kq_handle* h, dim3 grid, dim3 block, A... args) {
+    for (const KernelRow<Fn>& r : rows) if (r.sel == s) { hipLaunchKernelGGL(r.fn, grid, block, 0, h->stream, args...); return KQ_OK; }
+    return fail(KQ_ERR_INVALID, "%s has no instantiation <fmt %d, nbc %d, bin %d, kc %d, tpr %d, flag %d> (selector family %d)", family, s.fmt, s.nbc, s.bin, s.kc, s.tpr, (int)s.flag, (int)s.fam);
+}
+template <int B, int K> static KernelRow<decltype(&k_p1_hist<0, 0>)> p1h() { return {sel_of(K_P1_HIST, 0, 0, B, K), k_p1_hist<B, K>}; }
+template <int W, int N, int B, int K> static KernelRow<decltype(&k_p1_scatter<0, 512, 0, 0>)> p1w() { return {sel_of(K_P1_SCATTER, W, N, B, K), k_p1_scatter<W, N, B, K>}; }
+template <int B, int K, int T, bool TOP8 = false> static KernelRow<decltype(&k_p1_scatter_s<0, 0, 1>)> p1s() { return {sel_of(K_P1_SCATTER_S, 0, 0, B, K, T, TOP8), k_p1_scatter_s<B, K, T, TOP8>}; }
+template <int K> static KernelRow<decltype(&k_p1_scatter_c<0>)> p1c() { return {sel_of(K_P1_SCATTER_C, 0, 0, 0, K), k_p1_scatter_c<K>}; }
+template <int W> static KernelRow<decltype(&k_lv_hist<0>)> lvh() { return {sel_of(K_LV_HIST, W, 0, 0, 0), k_lv_hist<W>}; }
+template <int W, int N> static KernelRow<decltype(&k_lv_scatter<0, 512>)> lvw() { return {sel_of(K_LV_SCATTER, W, N, 0, 0), k_lv_scatter<W, N>}; }
+template <bool T> static KernelRow<decltype(&k_lv_scatter_s<false>)> lvs() { return {sel_of(K_LV_SCATTER_S, 0, 0, 0, 0, 0, T), k_lv_scatter_s<T>}; }
+template <int W, bool HOT> static KernelRow<decltype(&k_count_regions<0, false>)> p3g() { return {sel_of(K_COUNT_REGIONS, W, 0, 0, 0, 0, HOT), k_count_regions<W, HOT>}; }
+template <int K, bool T> static KernelRow<decltype(&k_count_regions_q4<0, false>)> p3q() { return {sel_of(K_COUNT_REGIONS_Q4, 0, 0, 0, K, 0, T), k_count_regions_q4<K, T>}; }
+template <int K, bool T> static KernelRow<decltype(&k_count_regions_q4r<0, false>)> p3r() { return {sel_of(K_COUNT_REGIONS_Q4R, 0, 0, 0, K, 0, T), k_count_regions_q4r<K, T>}; }
+template <int W> static KernelRow<decltype(&k_lookup_regions<0>)> lkr() { return {sel_of(K_LOOKUP_REGIONS, W, 0, 0, 0), k_lookup_regions<W>}; }
+
 extern "C" {
 
 const char* kq_last_error(void) { return g_err.c_str(); }
@@ -617,7 +639,7 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
             h->map_passes = (int)value; return KQ_OK;
         }
         case KQ_OPT_KERNEL_SET:
-            if (value < 0 || (value & ~(int64_t)(7 | 16 | 32 | 64 | 128))) return fail(KQ_ERR_INVALID, "KQ_OPT_KERNEL_SET is a mask of bits 1, 2, 4, 16, 32, 64, 128");
+            if (value < 0 || (value & ~(int64_t)KS_ALL)) return fail(KQ_ERR_INVALID, "KQ_OPT_KERNEL_SET is a mask of bits 1, 2, 4, 16, 32, 64, 128");
             h->kernel_set = (int)value; return KQ_OK;
         case KQ_OPT_OVERLAP:
             if (value < 0 || value > 2) return fail(KQ_ERR_INVALID, "KQ_OPT_OVERLAP must be 0, 1 or 2");
@@ -804,25 +826,49 @@ static void mark(kq_handle* h, const char* name) {
 }
 static void marks_reset(kq_handle* h) { h->marks.clear(); }
 
-static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t* ab, uint64_t lead, uint64_t len, EmitRange er, uint64_t* out,
-                   uint8_t* out_aux, int aux_fmt, const uint16_t* pinv = nullptr /*packed input: ab = the code words (tile_fetch)*/) {
-    // plain table split (no owner split, no map-range filter): branch-free bin functions
-    const bool plain = cfg.mode == 0 && cfg.filt_lo == 0 && cfg.filt_hi == cfg.map_count;
-    const bool owner_plain = cfg.mode == 1 && cfg.map_mask != 0 && cfg.filt_lo == 0 && cfg.filt_hi == cfg.map_count;   // multi-GPU owner split
-    const bool narrow_filt = cfg.mode == 0 && cfg.narrow && !plain && cfg.map_mask != 0 && h->k <= (int)NARROW_MAX_K;   // map-range pass on a bucketed table
-    const bool narrow_win = plain && cfg.narrow && (h->k <= (int)NARROW_MAX_K || h->k > PART_MAX_K) && (cfg.win_lo != 0 || cfg.win_hi != (1u << NARROW_CBITS));   // windowed table: own buckets only
-    const int binmode = owner_plain ? 3 : narrow_filt ? 4 : narrow_win ? 6 : !plain ? 0 : cfg.narrow ? 2 : 1;
+// the scanned sequence of a P1 pass; pinv != nullptr: packed input, ab = the code words (tile_fetch)
+struct P1Scan { const uint8_t* ab; uint64_t lead, len; EmitRange er; const uint16_t* pinv; };
+static int launch_p1_hist(kq_handle* h, const KernelSel& s, uint32_t grid, const P1Scan& in, const PartCfg& cfg, uint32_t g1, unsigned long long* m1) {
+    static const KernelRow<decltype(&k_p1_hist<0, 0>)> rows[] = {p1h<6, 21>(), p1h<6, 31>(), p1h<6, 0>(), p1h<2, 21>(), p1h<2, 0>(), p1h<1, 31>(), p1h<1, 0>(),
+                                                                  p1h<3, 21>(), p1h<3, 0>(), p1h<4, 21>(), p1h<4, 0>(), p1h<0, 0>(), p1h<5, 21>(), p1h<5, 0>()};
+    return launch_row(rows, "k_p1_hist", s, h, dim3(grid), dim3(TILE_THREADS), in.ab, in.lead, in.len, h->k, cfg, in.er, g1, m1, in.pinv);
+}
+static int launch_p1_scatter(kq_handle* h, const KernelSel& s, uint32_t grid, const P1Scan& in, const PartCfg& cfg, const unsigned long long* m1, uint64_t* out, uint8_t* out_aux, int aux_fmt) {
+    static const KernelRow<decltype(&k_p1_scatter<0, 512, 0, 0>)> wide[] = {
+        p1w<FMT_TOP8, 512, 6, 31>(), p1w<FMT_TOP8, 512, 6, 0>(), p1w<FMT_TOP8, 512, 2, 31>(), p1w<FMT_TOP8, 512, 2, 0>(), p1w<FMT_TOP8, 512, 0, 0>(),
+        p1w<FMT_NARROW, 512, 4, 21>(), p1w<FMT_NARROW, 512, 4, 0>(), p1w<FMT_NARROW, 512, 6, 21>(), p1w<FMT_NARROW, 512, 6, 0>(), p1w<FMT_NARROW, 512, 2, 21>(), p1w<FMT_NARROW, 512, 2, 0>(), p1w<FMT_NARROW, 512, 0, 0>(),
+        p1w<FMT_WIDE, 512, 1, 31>(), p1w<FMT_WIDE, NB_MAX, 1, 31>(), p1w<FMT_WIDE, 512, 0, 0>(), p1w<FMT_WIDE, NB_MAX, 0, 0>(),
+        p1w<FMT_PACK8, 512, 3, 21>(), p1w<FMT_PACK8, 512, 3, 0>(), p1w<FMT_PACK8, 512, 1, 0>(), p1w<FMT_PACK8, NB_MAX, 1, 0>(), p1w<FMT_PACK8, 512, 0, 0>(), p1w<FMT_PACK8, NB_MAX, 0, 0>()};
+    // the streamed scatter of 5-byte records (TPR tiles per round) and of hash-remainder records (TOP8)
+    static const KernelRow<decltype(&k_p1_scatter_s<0, 0, 1>)> streamed[] = {
+        p1s<4, 21, 1>(), p1s<4, 0, 1>(), p1s<6, 21, 1>(), p1s<6, 0, 1>(), p1s<2, 21, KQ_P1S_TPR>(), p1s<2, 0, KQ_P1S_TPR>(), p1s<0, 0, 1>(),
+        p1s<6, 31, 1, true>(), p1s<6, 0, 1, true>(), p1s<2, 31, 1, true>(), p1s<2, 0, 1, true>(), p1s<0, 0, 1, true>()};
+    static const KernelRow<decltype(&k_p1_scatter_c<0>)> compact[] = {p1c<21>(), p1c<0>()};
+    if (s.fam == K_P1_SCATTER_S) return launch_row(streamed, "k_p1_scatter_s", s, h, dim3(grid), dim3(TILE_THREADS * s.tpr), in.ab, in.lead, in.len, h->k, cfg, in.er, m1, (uint32_t*)out, out_aux, in.pinv);
+    if (s.fam == K_P1_SCATTER_C) return launch_row(compact, "k_p1_scatter_c", s, h, dim3(grid), dim3(TILE_THREADS), in.ab, in.lead, in.len, h->k, cfg, in.er, m1, (uint32_t*)out, out_aux, in.pinv);
+    return launch_row(wide, "k_p1_scatter", s, h, dim3(grid), dim3(TILE_THREADS), in.ab, in.lead, in.len, h->k, cfg, in.er, m1, out, out_aux, aux_fmt, in.pinv);
+}
+
+static int run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t* ab, uint64_t lead, uint64_t len, EmitRange er, uint64_t* out,
+                  uint8_t* out_aux, int aux_fmt, const uint16_t* pinv = nullptr /*packed input: ab = the code words (tile_fetch)*/) {
+    const P1Scan in{ab, lead, len, er, pinv};
+    const bool full_range = cfg.filt_lo == 0 && cfg.filt_hi == cfg.map_count, windowed = cfg.win_lo != 0 || cfg.win_hi != (1u << NARROW_CBITS);
+    const KernelSel hist = select_p1_hist(h->k, cfg.mode, cfg.narrow, cfg.map_mask, full_range, windowed);
+    const bool narrow_filt = hist.bin == 4, narrow_win = hist.bin == 6;      // map-range pass on a bucketed table; windowed table
     // KQ_OPT_COUNT_MAP_PASSES = n: this map-range pass is one of n over RESIDENT batches (the caller vouches that a batch keeps
     // its address and content between the passes).  The first pass that scans a slice counts for all n ranges in one histogram
     // launch (bin = range * 256 + bucket: the block of a range is contiguous in the bin-major matrix) and keeps the raw counts;
     // every pass takes its block from there -- (n - 1) of the n histogram scans of a slice are never run.
-    // the cached count matrix of `key`, or a fresh one of `bytes` bytes that `launch` fills; null: no room (4 GiB cap, hipMalloc)
-    auto cached_hist = [&](const kq_handle::HistKey& key, size_t bytes, auto launch) -> kq_handle::HistEntry* {
+    // the cached count matrix of `key`, or a fresh one of `bytes` bytes that a histogram over `all` fills; null: no room (4 GiB
+    // cap, hipMalloc) or, with rc set, no such kernel
+    int rc = KQ_OK;
+    auto cached_hist = [&](const kq_handle::HistKey& key, size_t bytes, const PartCfg& all) -> kq_handle::HistEntry* {
         for (auto& e : h->hist_cache) if (e.key == key) return &e;
         if (h->hist_cache_bytes + bytes > ((size_t)4 << 30)) return nullptr;
         DevMem buf;
         if (buf.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        launch(buf.as<unsigned long long>());
+        rc = launch_p1_hist(h, select_p1_hist_cached(h->k, hist.bin), p->g1, in, all, p->g1, buf.as<unsigned long long>());
+        if (rc) return nullptr;
         h->hist_cache.push_back(kq_handle::HistEntry{key, std::move(buf)});
         h->hist_cache_bytes += bytes;
         return &h->hist_cache.back();
@@ -832,74 +878,34 @@ static void run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t*
     if (narrow_filt && h->map_passes > 1 && P1_F == 1 && !h->hist_cache_off) {
         const uint32_t n = (uint32_t)h->map_passes, per = cfg.map_count / n, rr = cfg.filt_lo / per;
         if (cfg.filt_lo == rr * per && cfg.filt_hi == (rr + 1) * per) {
-            const auto* ent = cached_hist({ab, pinv, lead, len, er.lo, er.hi, p->g1, n, h->k}, n * block, [&](unsigned long long* buf) {
-                PartCfg all = cfg;
-                all.n_rng = n; all.n_coarse = n << NARROW_CBITS;
-                if (h->k == 21) hipLaunchKernelGGL((k_p1_hist<5, 21>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
-                else hipLaunchKernelGGL((k_p1_hist<5, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
-            });
-            if (ent) {
+            PartCfg all = cfg;
+            all.n_rng = n; all.n_coarse = n << NARROW_CBITS;
+            if (const auto* ent = cached_hist({ab, pinv, lead, len, er.lo, er.hi, p->g1, n, h->k}, n * block, all)) {
                 (void)hipMemcpyAsync(p->m1, ent->m1_all.as<char>() + rr * block, block, hipMemcpyDeviceToDevice, h->stream);
                 have_hist = true;
             }
         }
     }
-    // the same for bucket-range passes (windowed table): the unfiltered bucket matrix serves every window -- the rows of the
-    // other buckets are zeroed before the scan
+    // the same for bucket-range passes (windowed table): the unfiltered bucket matrix (any k: hash-remainder records too) serves
+    // every window -- the rows of the other buckets are zeroed before the scan
     if (narrow_win && h->map_passes > 1 && P1_F == 1 && !h->hist_cache_off) {
-        const auto* ent = cached_hist({ab, pinv, lead, len, er.lo, er.hi, p->g1, 0xB0C4E7u, h->k}, block, [&](unsigned long long* buf) {
-            PartCfg all = cfg;
-            all.win_lo = 0; all.win_hi = 1u << NARROW_CBITS;
-            if (h->k == 21) hipLaunchKernelGGL((k_p1_hist<2, 21>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);
-            else hipLaunchKernelGGL((k_p1_hist<2, 0>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, all, er, p->g1, buf, pinv);      // (any k: hash-remainder records too)
-        });
-        if (ent) {
+        PartCfg all = cfg;
+        all.win_lo = 0; all.win_hi = 1u << NARROW_CBITS;
+        if (const auto* ent = cached_hist({ab, pinv, lead, len, er.lo, er.hi, p->g1, 0xB0C4E7u, h->k}, block, all)) {
             (void)hipMemcpyAsync(p->m1, ent->m1_all.get(), block, hipMemcpyDeviceToDevice, h->stream);
             if (cfg.win_lo) (void)hipMemsetAsync(p->m1, 0, (size_t)cfg.win_lo * row, h->stream);
             if (cfg.win_hi < (1u << NARROW_CBITS)) (void)hipMemsetAsync((char*)p->m1 + (size_t)cfg.win_hi * row, 0, (size_t)((1u << NARROW_CBITS) - cfg.win_hi) * row, h->stream);
             have_hist = true;
         }
     }
-#define KQ_P1H(B, K) hipLaunchKernelGGL((k_p1_hist<B, K>), dim3(p->g1 * P1_F), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, cfg, er, p->g1, p->m1, pinv)
-    if (have_hist) { }
-    else if (binmode == 6) { if (h->k == 21) KQ_P1H(6, 21); else if (h->k == 31) KQ_P1H(6, 31); else KQ_P1H(6, 0); }
-    else if (binmode == 2) { if (h->k == 21) KQ_P1H(2, 21); else KQ_P1H(2, 0); }
-    else if (binmode == 1) { if (h->k == 31) KQ_P1H(1, 31); else KQ_P1H(1, 0); }
-    else if (binmode == 3) { if (h->k == 21) KQ_P1H(3, 21); else KQ_P1H(3, 0); }
-    else if (binmode == 4) { if (h->k == 21) KQ_P1H(4, 21); else KQ_P1H(4, 0); }
-    else KQ_P1H(0, 0);
-#undef KQ_P1H
+    if (!rc && !have_hist) rc = launch_p1_hist(h, hist, p->g1 * P1_F, in, cfg, p->g1, p->m1);
+    if (rc) return rc;
     scan_u64(h, p->m1, (uint64_t)cfg.n_coarse * p->g1 * P1_F, p->sums, p->total);
     hipLaunchKernelGGL(k_p1_offsets, dim3((cfg.n_coarse + 256) / 256), dim3(256), 0, h->stream, p->m1, p->total, cfg, p->g1, p->seg_off);
     mark(h, "k_p1_hist+scan");
-    const bool small = cfg.n_coarse < 512;                     // 48 KiB LDS variant: three workgroups per CU
-#define KQ_P1S(W, N, B, K) hipLaunchKernelGGL((k_p1_scatter<W, N, B, K>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, cfg, er, p->m1, out, out_aux, aux_fmt, pinv)
-#define KQ_P1T(B, K) do { if (h->kernel_set & 1) KQ_P1S(FMT_TOP8, 512, B, K); else \
-        hipLaunchKernelGGL((k_p1_scatter_s<B, K, 1, true>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, cfg, er, p->m1, (uint32_t*)out, out_aux, pinv); } while (0)
-    // hash-remainder records (k = 29..32); a windowed table drops the k-mers of foreign buckets here, like the narrow scatter below
-    if (cfg.narrow && h->k > PART_MAX_K) {
-        if (narrow_win) { if (h->k == 31) KQ_P1T(6, 31); else KQ_P1T(6, 0); }
-        else if (plain && h->k == 31) KQ_P1T(2, 31); else if (plain) KQ_P1T(2, 0); else KQ_P1T(0, 0);
-    }
-    // narrow records: the streamed scatter (k_p1_scatter_s); a pass that keeps every k-mer splits two tiles per round, a filtered one one
-#define KQ_P1N(B, K, T) do { if (h->kernel_set & 1) KQ_P1S(FMT_NARROW, 512, B, K); else \
-        hipLaunchKernelGGL((k_p1_scatter_s<B, K, T>), dim3(p->g1), dim3(TILE_THREADS * T), 0, h->stream, ab, lead, len, h->k, cfg, er, p->m1, (uint32_t*)out, out_aux, pinv); } while (0)
-    // behind the map-range filter: survivors compacted ahead of the hash (k_p1_scatter_c); kernel_set bit 128 = the previous kernel
-#define KQ_P1C(K) do { if (h->kernel_set & (1 | 128)) KQ_P1N(4, K, 1); else \
-        hipLaunchKernelGGL((k_p1_scatter_c<K>), dim3(p->g1), dim3(TILE_THREADS), 0, h->stream, ab, lead, len, h->k, cfg, er, p->m1, (uint32_t*)out, out_aux, pinv); } while (0)
-    else if (narrow_filt)  { if (h->k == 21) KQ_P1C(21); else KQ_P1C(0); }
-    else if (narrow_win)   { if (h->k == 21) KQ_P1N(6, 21, 1); else KQ_P1N(6, 0, 1); }
-    else if (cfg.narrow)   { if (plain && h->k == 21) KQ_P1N(2, 21, KQ_P1S_TPR); else if (plain) KQ_P1N(2, 0, KQ_P1S_TPR); else KQ_P1N(0, 0, 1); }     // 256 buckets
-    else if (out_aux && plain && h->k == 31) { if (small) KQ_P1S(FMT_WIDE, 512, 1, 31); else KQ_P1S(FMT_WIDE, NB_MAX, 1, 31); }   // the HiFi k
-    else if (out_aux) { if (small) KQ_P1S(FMT_WIDE, 512, 0, 0); else KQ_P1S(FMT_WIDE, NB_MAX, 0, 0); }
-    else if (owner_plain && !out_aux && small) { if (h->k == 21) KQ_P1S(FMT_PACK8, 512, 3, 21); else KQ_P1S(FMT_PACK8, 512, 3, 0); }
-    else if (plain)   { if (small) KQ_P1S(FMT_PACK8, 512, 1, 0); else KQ_P1S(FMT_PACK8, NB_MAX, 1, 0); }
-    else              { if (small) KQ_P1S(FMT_PACK8, 512, 0, 0); else KQ_P1S(FMT_PACK8, NB_MAX, 0, 0); }
-#undef KQ_P1S
-#undef KQ_P1N
-#undef KQ_P1C
-#undef KQ_P1T
+    rc = launch_p1_scatter(h, select_p1_scatter(h->k, cfg.mode, cfg.narrow, cfg.map_mask, full_range, windowed, out_aux != nullptr, cfg.n_coarse, KQ_P1S_TPR, h->kernel_set), p->g1, in, cfg, p->m1, out, out_aux, aux_fmt);
     mark(h, "k_p1_scatter");
+    return rc;
 }
 // The input of a split level: records (+ lockstep bytes) grouped in segments [seg_lo[i], seg_hi[i]).  n_seg / spb (segments per
 // hash-prefix bucket) matter to sort_to_regions only, whose first level may read runs that are not the plan's own
@@ -913,23 +919,32 @@ static LevelCfg with_rep_shift(const LevelCfg& lv) {
     while (lvr.rep_shift < 6 && (((uint64_t)lv.nb + 1) << (lvr.rep_shift + 1)) <= 512) ++lvr.rep_shift;
     return lvr;
 }
+// what the unit kernels of a level read: the input records and segments, the level and the unit table
+struct LevelUnits { const uint64_t* in; const uint8_t* in_aux; LevelCfg lv; const unsigned long long *seg_lo, *seg_hi, *unit_base; uint32_t* m2; unsigned grid; };
+static int launch_level_hist(kq_handle* h, const KernelSel& s, const LevelUnits& u) {
+    static const KernelRow<decltype(&k_lv_hist<0>)> rows[] = {lvh<FMT_TOP8>(), lvh<FMT_NARROW>(), lvh<FMT_WIDE>(), lvh<FMT_PACK8>()};
+    return launch_row(rows, "k_lv_hist", s, h, dim3(u.grid), dim3(MS_THREADS), u.in, u.in_aux, u.lv, u.seg_lo, u.seg_hi, u.unit_base, u.m2);
+}
+static int launch_level_scatter(kq_handle* h, const KernelSel& s, const LevelUnits& u, const unsigned long long* gb, uint64_t* out, uint8_t* out_aux) {
+    static const KernelRow<decltype(&k_lv_scatter<0, 512>)> rows[] = {
+        lvw<FMT_PACK8_TO_NARROW, 512>(), lvw<FMT_TOP8, 512>(), lvw<FMT_TOP8, NB_MAX>(), lvw<FMT_NARROW_TO_TIGHT, 512>(), lvw<FMT_NARROW_TO_TIGHT, NB_MAX>(),
+        lvw<FMT_NARROW, 512>(), lvw<FMT_NARROW, NB_MAX>(), lvw<FMT_WIDE, 512>(), lvw<FMT_WIDE, NB_MAX>(), lvw<FMT_PACK8, 512>(), lvw<FMT_PACK8, NB_MAX>()};
+    static const KernelRow<decltype(&k_lv_scatter_s<false>)> streamed[] = {lvs<true>(), lvs<false>()};
+    if (s.fam == K_LV_SCATTER_S) return launch_row(streamed, "k_lv_scatter_s", s, h, dim3(u.grid), dim3(LV_THREADS), (const uint32_t*)u.in, u.in_aux, u.lv, u.seg_lo, u.seg_hi, u.unit_base, u.m2, gb, (uint32_t*)out, out_aux);
+    return launch_row(rows, "k_lv_scatter", s, h, dim3(u.grid), dim3(LV_THREADS), u.in, u.in_aux, u.lv, u.seg_lo, u.seg_hi, u.unit_base, u.m2, gb, out, out_aux);
+}
 // one generic split level: src -> out grouped by (segment, bin); afterwards gb[0..n_seg*nb] are the output offsets
-static void run_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const LevelIn& src, uint64_t* out, uint8_t* out_aux,
-                      unsigned long long* gb = nullptr /*where the output offsets go (default p->group_base)*/) {
+static int run_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const LevelIn& src, uint64_t* out, uint8_t* out_aux,
+                     unsigned long long* gb = nullptr /*where the output offsets go (default p->group_base)*/) {
     if (!gb) gb = p->group_base;
-    const uint64_t* in = src.recs; const uint8_t* in_aux = src.aux;
-    const unsigned long long *seg_lo = src.seg_lo, *seg_hi = src.seg_hi;
     const LevelCfg lv_ = with_rep_shift(lv);
-    const int fmt = lv.narrow == 2 ? FMT_TOP8 : lv.narrow ? FMT_NARROW : in_aux != nullptr ? FMT_WIDE : FMT_PACK8;       // input format; lv.top8: packed in, narrow out
     const uint64_t groups = (uint64_t)(lv.n_seg / lv.spb) * lv.nb;
-    hipLaunchKernelGGL(k_lv_units, dim3(1), dim3(1024), 0, h->stream, seg_lo, seg_hi, lv_, p->unit_base);
+    hipLaunchKernelGGL(k_lv_units, dim3(1), dim3(1024), 0, h->stream, src.seg_lo, src.seg_hi, lv_, p->unit_base);
     // one workgroup per work unit (upper bound of the unit count; surplus workgroups exit at once):
     // the hardware dispatcher balances them, a fixed grid looping over units left a 30 % tail
-    const unsigned unit_grid = (unsigned)std::min<uint64_t>(p->n_max / P2_UNIT + lv.n_seg + 1, 1u << 30);
-    if (fmt == FMT_TOP8) hipLaunchKernelGGL(k_lv_hist<FMT_TOP8>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, seg_lo, seg_hi, p->unit_base, p->m2);
-    else if (fmt == FMT_NARROW) hipLaunchKernelGGL(k_lv_hist<FMT_NARROW>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, seg_lo, seg_hi, p->unit_base, p->m2);
-    else if (fmt == FMT_WIDE) hipLaunchKernelGGL(k_lv_hist<FMT_WIDE>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, seg_lo, seg_hi, p->unit_base, p->m2);
-    else hipLaunchKernelGGL(k_lv_hist<FMT_PACK8>, dim3(unit_grid), dim3(MS_THREADS), 0, h->stream, in, in_aux, lv_, seg_lo, seg_hi, p->unit_base, p->m2);
+    const LevelUnits u{src.recs, src.aux, lv_, src.seg_lo, src.seg_hi, p->unit_base, p->m2, (unsigned)std::min<uint64_t>(p->n_max / P2_UNIT + lv.n_seg + 1, 1u << 30)};
+    int rc = launch_level_hist(h, select_level_hist(lv.narrow, src.aux != nullptr), u);
+    if (rc) return rc;
     // few units per segment (many segments): one thread per group; else one wave per group (a segment of thousands of units)
     if (p->n_max / P2_UNIT + 1 <= 8 * (uint64_t)(lv.n_seg / lv.spb))
         hipLaunchKernelGGL(k_lv_offsets_thread, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, h->stream, p->m2, lv_, p->unit_base, gb);
@@ -938,27 +953,12 @@ static void run_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const Level
     (void)hipMemsetAsync(gb + groups, 0, 8, h->stream);   // failure surfaces at the caller's hipGetLastError
     scan_u64(h, gb, groups + 1, p->sums, p->total + 1);
     mark(h, "k_lv_hist+offsets+scan");
-    const bool small = lv.nb < 512;
-#define KQ_LVS(W, N) hipLaunchKernelGGL((k_lv_scatter<W, N>), dim3(unit_grid), dim3(LV_THREADS), 0, h->stream, in, in_aux, lv_, \
-                                        seg_lo, seg_hi, p->unit_base, p->m2, gb, out, out_aux)
-    if (lv.top8)              { KQ_LVS(FMT_PACK8_TO_NARROW, 512); }
-    else if (fmt == FMT_TOP8) { if (small) KQ_LVS(FMT_TOP8, 512); else KQ_LVS(FMT_TOP8, NB_MAX); }
-    // narrow records, at most 512 (bin, replica) counters: the streamed scatter (k_lv_scatter_s) for the level that writes tight records
-#define KQ_LVN(T) hipLaunchKernelGGL((k_lv_scatter_s<T>), dim3(unit_grid), dim3(LV_THREADS), 0, h->stream, (const uint32_t*)in, in_aux, lv_, \
-                                      seg_lo, seg_hi, p->unit_base, p->m2, gb, (uint32_t*)out, out_aux)
-    else if (fmt == FMT_NARROW && small && lv.rstart && !(h->kernel_set & 4)) { KQ_LVN(true); }
-    else if (fmt == FMT_NARROW && small && !lv.rstart && (h->kernel_set & 2)) { KQ_LVN(false); }     // (measured: 0 .. +8 % against k_lv_scatter; not the default)
-#undef KQ_LVN
-    else if (fmt == FMT_NARROW && lv.rstart) { if (small) KQ_LVS(FMT_NARROW_TO_TIGHT, 512); else KQ_LVS(FMT_NARROW_TO_TIGHT, NB_MAX); }
-    else if (fmt == FMT_NARROW) { if (small) KQ_LVS(FMT_NARROW, 512); else KQ_LVS(FMT_NARROW, NB_MAX); }
-    else if (fmt == FMT_WIDE) { if (small) KQ_LVS(FMT_WIDE, 512); else KQ_LVS(FMT_WIDE, NB_MAX); }
-    else                      { if (small) KQ_LVS(FMT_PACK8, 512); else KQ_LVS(FMT_PACK8, NB_MAX); }
-#undef KQ_LVS
+    rc = launch_level_scatter(h, select_level_scatter(lv.narrow, src.aux != nullptr, lv.top8 != 0, lv.nb, lv.rstart != nullptr, h->kernel_set), u, gb, out, out_aux);
     mark(h, "k_lv_scatter");
+    return rc;
 }
 // The last level of a plan with a middle level, narrow records in and tight records out, fewer than 512 regions per segment: one
 // workgroup per segment counts, offsets and splits it (k_lv_segment_s).  Same output and same gb as run_level.
-static bool segment_level_ok(const PartPlan& p, const LevelCfg& lv) { return p.fmt == FMT_NARROW && lv.narrow == 1 && lv.rstart && lv.nr_shift != 0 && lv.nb < 512 && lv.spb == 1; }
 static void run_segment_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, const uint64_t* in, const uint8_t* in_aux, uint64_t* out, unsigned long long* gb) {
     mark(h, "segment_level");                                     // (zero-length: tells a reader of the stage list which form ran)
     mark(h, "k_lv_hist+offsets+scan");                            // (no such stage here: the name stays so that stage_ms adds up)
@@ -1113,6 +1113,16 @@ static uint32_t* roff_take(kq_handle* h) {
     if (h->roff.bytes() < need && h->roff.alloc(need) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     return h->roff.as<uint32_t>();
 }
+// one kernel of the table pass over the pending sets; `rows`: the region-major offset matrix (k_count_regions_q4r only)
+static int launch_table_pass(kq_handle* h, const KernelSel& s, dim3 grid, const Q4SetsRow& rows, int empty, unsigned long long* hot, uint32_t rps) {
+    static const KernelRow<decltype(&k_count_regions<0, false>)> generic[] = {p3g<FMT_TOP8, false>(), p3g<FMT_WIDE, false>(), p3g<FMT_PACK8, false>(), p3g<FMT_NARROW, true>(), p3g<FMT_TOP8, true>(), p3g<FMT_WIDE, true>(), p3g<FMT_PACK8, true>()};
+    static const KernelRow<decltype(&k_count_regions_q4<0, false>)> compact[] = {p3q<21, true>(), p3q<0, true>(), p3q<21, false>(), p3q<0, false>()};
+    static const KernelRow<decltype(&k_count_regions_q4r<0, false>)> matrix[] = {p3r<21, true>(), p3r<0, true>(), p3r<21, false>(), p3r<0, false>()};
+    const P3Set* sets = h->d_sets.as<P3Set>();
+    if (s.fam == K_COUNT_REGIONS_Q4R) return launch_row(matrix, "k_count_regions_q4r", s, h, grid, dim3(Q4_THREADS), h->view(), rows, empty, hot, rps);
+    if (s.fam == K_COUNT_REGIONS_Q4) return launch_row(compact, "k_count_regions_q4", s, h, grid, dim3(Q4_THREADS), h->view(), sets, (uint32_t)h->n_pend, empty, hot, rps);
+    return launch_row(generic, "k_count_regions", s, h, grid, dim3(P3_THREADS), h->view(), sets, (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps);
+}
 static int flush_pending_base(kq_handle* h) {
     const uint64_t R = h->n_regions;
     HIPC(h->hot.ensure((size_t)(R + 2) * 8));
@@ -1124,21 +1134,17 @@ static int flush_pending_base(kq_handle* h) {
     }
     unsigned long long* hot = h->hot.as<unsigned long long>();     // [0] = count, then up to R region ids
     HIPC(hipMemsetAsync(hot, 0, 8, h->stream));
-    const dim3 grid((unsigned)std::min<uint64_t>(h->n_alloc_regions(), 1u << 30)), grid_hot(h->n_cu), block(P3_THREADS);   // one workgroup per (allocated) region: dispatcher-balanced
+    const dim3 grid((unsigned)std::min<uint64_t>(h->n_alloc_regions(), 1u << 30)), grid_hot(h->n_cu);   // one workgroup per (allocated) region: dispatcher-balanced
     // 1: the slot array holds the empty image (skip reading it); 2: logically empty but not initialised (lazy kq_clear):
     // also write the image of regions without records.  A dirty array is never read, whatever table_empty says
     const int empty = h->slots_dirty ? 2 : h->table_empty ? 1 : 0;
     const int fmt = h->pend_fmt;
     const uint32_t rps = (fmt == FMT_NARROW || fmt == FMT_TIGHT || fmt == FMT_TOP8) ? (uint32_t)(R >> NARROW_CBITS) : 1u;
-#define KQ_HOT(F) hipLaunchKernelGGL((k_count_regions<F, true>), grid_hot, block, 0, h->stream, h->view(), h->d_sets.as<P3Set>(), (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps)
-#define KQ_P3(F) do { \
-        hipLaunchKernelGGL((k_count_regions<F, false>), grid, block, 0, h->stream, h->view(), h->d_sets.as<P3Set>(), (uint32_t)h->n_pend, h->pend_aux_fmt, empty, hot, rps); \
-        KQ_HOT(F); } while (0)
     // 4- and 5-byte records: the sets' region offsets are transposed first, the pass reads one row pair per region and adds the
     // regions' totals to TOT_LINES lines, which k_fold_totals adds to the table state behind it (KQ_OPT_KERNEL_SET bit 16, or no
     // memory for the matrix: the previous pass -- the sets' own offset arrays, two atomics per region on the table state)
     Q4SetsRow rows = {};
-    if ((fmt == FMT_TIGHT || fmt == FMT_NARROW) && !(h->kernel_set & 16)) {
+    if (table_pass_wants_matrix(fmt, h->kernel_set)) {
         if (uint32_t* roff = roff_take(h)) {
             rows.pitch = roff_pitch((uint32_t)h->n_pend);
             if (!h->tot) {
@@ -1154,21 +1160,11 @@ static int flush_pending_base(kq_handle* h) {
                                roff, h->d_sets.as<P3Set>(), (uint32_t)h->n_pend, rows.pitch, h->reg_lo(), n_rows);
         }
     }
-#define KQ_Q4(KC, T) do { \
-        if (rows.roff) hipLaunchKernelGGL((k_count_regions_q4r<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), rows, empty, hot, rps); \
-        else hipLaunchKernelGGL((k_count_regions_q4<KC, T>), grid, dim3(Q4_THREADS), 0, h->stream, h->view(), h->d_sets.as<P3Set>(), (uint32_t)h->n_pend, empty, hot, rps); \
-        KQ_HOT(FMT_NARROW); \
-        if (rows.roff && rows.tot) hipLaunchKernelGGL(k_fold_totals, dim3(1), dim3(256), 0, h->stream, rows.tot, h->d_state()); } while (0)
-    // ordinary regions of 4- and 5-byte records: the compact 32-bit-key kernel; skewed ones: the generic folding kernel
-    // (pend_aux_fmt == AUX_TIGHT tells it about FMT_TIGHT sets)
-    if (fmt == FMT_TIGHT)       { if (h->k == 21) KQ_Q4(21, true); else KQ_Q4(0, true); }
-    else if (fmt == FMT_NARROW) { if (h->k == 21) KQ_Q4(21, false); else KQ_Q4(0, false); }
-    else if (fmt == FMT_TOP8) KQ_P3(FMT_TOP8);
-    else if (fmt == FMT_WIDE) KQ_P3(FMT_WIDE);
-    else KQ_P3(FMT_PACK8);
-#undef KQ_Q4
-#undef KQ_P3
-#undef KQ_HOT
+    // ordinary regions, then the skewed ones the pass listed
+    rc = launch_table_pass(h, select_table_pass(fmt, h->k, rows.roff != nullptr), grid, rows, empty, hot, rps);
+    if (!rc) rc = launch_table_pass(h, select_hot_pass(fmt), grid_hot, rows, empty, hot, rps);
+    if (rc) return rc;
+    if (rows.roff && rows.tot) hipLaunchKernelGGL(k_fold_totals, dim3(1), dim3(256), 0, h->stream, rows.tot, h->d_state());
     h->n_pend = 0; h->arena_used = 0; h->pend_records = 0;
     ++h->table_passes;
     // only now (every failure path of the partition stages lies before this point): the table has content, and a lazily
@@ -1200,8 +1196,9 @@ static int dest_take(kq_handle* h, const PartPlan& p, uint64_t n_max, Dest* d) {
 //   5-byte / hash-remainder records (FMT_NARROW / FMT_TOP8): bucket -> regions (bucket b owns regions [b * nb, (b + 1) * nb)),
 //     in one level or, for plans with sub_bits, bucket -> sub-bucket -> regions
 //   packed / wide records: coarse bucket -> regions, or nothing at all when the bins were the regions themselves
-static P3Set sort_to_regions(kq_handle* h, PartPlan* p, const LevelIn& in, const Dest& d) {
+static int sort_to_regions(kq_handle* h, PartPlan* p, const LevelIn& in, const Dest& d, P3Set* set) {
     const bool arena = d.in_arena();
+    int rc = KQ_OK;
     uint64_t* fin = arena ? d.recs : p->recs2;
     uint8_t* fin_aux = arena ? d.aux : p->a2();
     unsigned long long* fin_base = arena ? d.base : p->group_base;
@@ -1216,27 +1213,28 @@ static P3Set sort_to_regions(kq_handle* h, PartPlan* p, const LevelIn& in, const
         if (d.tight) last.rstart = h->rstart.as<uint32_t>();
         if (sb == 0) {
             last.n_seg = in.n_seg; last.spb = in.spb;
-            run_level(h, p, last, in, fin, fin_aux, fin_base);
+            rc = run_level(h, p, last, in, fin, fin_aux, fin_base);
         } else {
             LevelCfg mid = level_narrow(p->cfg, sb, true, t8);
             mid.n_seg = in.n_seg; mid.spb = in.spb;
             uint64_t* m = mid_to_2 ? p->recs2 : p->recs1;
             uint8_t* m_aux = mid_to_2 ? p->a2() : p->a1();
-            run_level(h, p, mid, in, m, m_aux);
+            rc = run_level(h, p, mid, in, m, m_aux);
+            if (rc) return rc;
             (void)hipMemcpyAsync(p->seg_off, p->group_base, (size_t)(((1u << NARROW_CBITS) << sb) + 1) * 8, hipMemcpyDeviceToDevice, h->stream);
-            // KQ_OPT_KERNEL_SET: 64 = the segment kernel wherever it applies, 32 = never; else the slice's buckets decide (a hot
-            // sub-bucket keeps the unit path, which splits it over many workgroups)
-            if (segment_level_ok(*p, last) && ((h->kernel_set & 64) || (p->even_buckets && !(h->kernel_set & 32))))
+            if (select_last_level(p->fmt, last.narrow, last.rstart != nullptr, last.nr_shift, last.nb, last.spb, p->even_buckets, h->kernel_set).fam == K_LV_SEGMENT_S)
                 run_segment_level(h, p, last, m, m_aux, fin, fin_base);
             else
-                run_level(h, p, last, own_segments(*p, m, m_aux, last.n_seg), fin, fin_aux, fin_base);
+                rc = run_level(h, p, last, own_segments(*p, m, m_aux, last.n_seg), fin, fin_aux, fin_base);
         }
     } else if (p->two_level) {
-        run_level(h, p, level_coarse_to_regions(p->cfg), in, fin, fin_aux, fin_base);
+        rc = run_level(h, p, level_coarse_to_regions(p->cfg), in, fin, fin_aux, fin_base);
     } else {
-        return P3Set{in.recs, in.aux, in.seg_lo, p->n_max};          // bins were the regions themselves
+        *set = P3Set{in.recs, in.aux, in.seg_lo, p->n_max};          // bins were the regions themselves
+        return KQ_OK;
     }
-    return P3Set{fin, fin_aux, fin_base, arena ? d.n_max : p->n_max};
+    *set = P3Set{fin, fin_aux, fin_base, arena ? d.n_max : p->n_max};
+    return rc;
 }
 
 // make `set` part of the next table pass; a set in the scratch buffers is applied at once (the scratch is reused by the next slice)
@@ -1245,6 +1243,10 @@ static int submit(kq_handle* h, const P3Set& set, const Dest& d) {
     int rc = pend_add(h, set, d.fmt, d.aux_fmt);
     if (rc) return rc;
     return d.in_arena() ? KQ_OK : flush_pending(h);
+}
+static int sort_and_submit(kq_handle* h, PartPlan* p, const LevelIn& in, const Dest& d) {
+    P3Set set; int rc = sort_to_regions(h, p, in, d, &set);
+    return rc ? rc : submit(h, set, d);
 }
 
 // the plan of a scanned sequence (count, region-wise lookup): 5-byte records up to k = 21 and 8-byte hash-remainder records
@@ -1273,7 +1275,8 @@ static int count_partitioned(kq_handle* h, const uint8_t* ab, uint64_t lead, uin
     if (leveled && !filtered) { rc = dest_take(h, p, p.n_max, &dst); if (rc) return rc; }
     marks_reset(h);
     mark(h, "start");
-    run_p1(h, &p, p.cfg, ab, lead, len, er, p.recs1, p.a1(), AUX_IDX6, pinv);
+    rc = run_p1(h, &p, p.cfg, ab, lead, len, er, p.recs1, p.a1(), AUX_IDX6, pinv);
+    if (rc) return rc;
     if (leveled && filtered) {
         // (5-byte records with a middle level: the 257 bucket offsets come with the count, p.seg_off[256] = *p.total -- the
         // last level's kernel depends on how even the buckets are, kq_seg_gate_host.h)
@@ -1287,7 +1290,7 @@ static int count_partitioned(kq_handle* h, const uint8_t* ab, uint64_t lead, uin
         if (with_offsets) { n_recs = offs[NBK]; p.even_buckets = kq::seg_gate_even(offs, NBK); }
         rc = dest_take(h, p, std::min<uint64_t>(p.n_max, ((uint64_t)n_recs + 15) & ~7ull), &dst); if (rc) return rc;
     }
-    return submit(h, sort_to_regions(h, &p, own_segments(p, p.recs1, p.a1(), p.cfg.n_coarse), dst), dst);
+    return sort_and_submit(h, &p, own_segments(p, p.recs1, p.a1(), p.cfg.n_coarse), dst);
 }
 // partitioned count of n records already on the device (multi-GPU receive side, kq_insert_records_dev).
 // d_aux == nullptr: packed 8-byte records; else WIDE records with d_aux in `aux_fmt`.
@@ -1308,14 +1311,15 @@ static int count_partitioned_records(kq_handle* h, const uint64_t* d_recs, const
         first.in_raw = raw ? 1 : 0; first.k = (uint32_t)h->k;
     }
     hipLaunchKernelGGL(k_set2, dim3(1), dim3(1), 0, h->stream, p.seg_off, 0ull, (unsigned long long)n);
-    run_level(h, &p, first, own_segments(p, d_recs, d_aux, 1), p.recs1, p.a1());        // group_base = coarse offsets
+    rc = run_level(h, &p, first, own_segments(p, d_recs, d_aux, 1), p.recs1, p.a1());        // group_base = coarse offsets
+    if (rc) return rc;
     LevelIn coarse{p.recs1, p.a1(), p.group_base, p.group_base + 1, p.cfg.n_coarse, 1};
     if (p.two_level) {
         // the coarse offsets become the segment table of the next level
         HIPC(hipMemcpyAsync(p.seg_off, p.group_base, (size_t)(p.cfg.n_coarse + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
         coarse = own_segments(p, p.recs1, p.a1(), p.cfg.n_coarse);
     }
-    return submit(h, sort_to_regions(h, &p, coarse, dst), dst);
+    return sort_and_submit(h, &p, coarse, dst);
 }
 
 // the k-mer starts [a, b) of a resident sequence as a scan of their own (the margins: see count_seq_dev): ASCII bytes
@@ -1729,9 +1733,16 @@ int kq_emit_records(kq_handle* h, const char* bases, uint64_t len, uint64_t* key
     return rc;
 }
 
-// owner split of a resident batch (multi-GPU staging): records grouped by owner part in d_recs; d_edges != nullptr: WIDE
-// records (raw key + reference edge byte), else packed 8-byte records
-static int owner_split(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint8_t* d_edges, uint64_t* part_counts) {
+// owner split of a resident batch (multi-GPU staging): records grouped by owner part in d_recs.  `packed`: packed 8-byte records
+// (kq_emit_packed_dev), else WIDE records (raw key + reference edge byte in d_edges, kq_emit_partitioned_dev)
+static int owner_split(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint8_t* d_edges, bool packed, uint64_t cap, uint64_t* part_counts) {
+    if (!h || !part_counts || n_parts < 1 || n_parts > h->map_count || n_parts >= NB_MAX || (!d_bases && len)) return fail(KQ_ERR_INVALID, "bad argument");
+    if (packed && h->k > PART_MAX_K) return fail(KQ_ERR_INVALID, "packed 8-byte records need k <= %d (use kq_emit_partitioned_dev)", PART_MAX_K);
+    HIPC(hipSetDevice(h->device));
+    for (int i = 0; i < n_parts; ++i) part_counts[i] = 0;
+    if (len < (uint64_t)h->k) return KQ_OK;
+    if (len - h->k + 1 >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "an owner split handles fewer than 2^32 k-mer starts per call (got %llu): cut the batch", (unsigned long long)(len - h->k + 1));
+    if (cap < len - h->k + 1 || !d_recs || (!packed && !d_edges)) return fail(KQ_ERR_CAPACITY, "record buffer too small: need room for %llu records", (unsigned long long)(len - h->k + 1));
     const uint8_t* ab; uint64_t lead;
     aligned_view(d_bases, &ab, &lead);
     PartPlan p;
@@ -1743,8 +1754,9 @@ static int owner_split(kq_handle* h, const char* d_bases, uint64_t len, int n_pa
     if (rc) return rc;
     PartCfg cfg = p.cfg;
     cfg.mode = 1; cfg.n_coarse = bins; cfg.owner_sub = sb;
-    if (d_edges) cfg.raw_out = 1;
-    run_p1(h, &p, cfg, ab, lead, len, EmitRange{0, ~0ull}, d_recs, d_edges, d_edges ? AUX_EDGE_BYTE : AUX_IDX6);
+    if (!packed) cfg.raw_out = 1;
+    rc = run_p1(h, &p, cfg, ab, lead, len, EmitRange{0, ~0ull}, d_recs, packed ? nullptr : d_edges, packed ? AUX_IDX6 : AUX_EDGE_BYTE);
+    if (rc) return rc;
     std::vector<unsigned long long> off((size_t)bins + 1);
     HIPC(hipMemcpyAsync(off.data(), p.seg_off, off.size() * 8, hipMemcpyDeviceToHost, h->stream));
     HIPC(hipStreamSynchronize(h->stream));
@@ -1752,31 +1764,11 @@ static int owner_split(kq_handle* h, const char* d_bases, uint64_t len, int n_pa
     return KQ_OK;
 }
 
-int kq_emit_partitioned_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_keys, uint8_t* d_edges,
-                            uint64_t cap, uint64_t* part_counts) {
-    if (!h || !part_counts || n_parts < 1 || n_parts > h->map_count || n_parts >= NB_MAX || (!d_bases && len))
-        return fail(KQ_ERR_INVALID, "bad argument");
-    HIPC(hipSetDevice(h->device));
-    for (int i = 0; i < n_parts; ++i) part_counts[i] = 0;
-    if (len < (uint64_t)h->k) return KQ_OK;
-    if (len - h->k + 1 >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "an owner split handles fewer than 2^32 k-mer starts per call (got %llu): cut the batch", (unsigned long long)(len - h->k + 1));
-    if (cap < len - h->k + 1 || !d_keys || !d_edges) return fail(KQ_ERR_CAPACITY, "record buffer too small: need room for %llu records",
-                                                                  (unsigned long long)(len - h->k + 1));
-    return owner_split(h, d_bases, len, n_parts, d_keys, d_edges, part_counts);
+int kq_emit_partitioned_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_keys, uint8_t* d_edges, uint64_t cap, uint64_t* part_counts) {
+    return owner_split(h, d_bases, len, n_parts, d_keys, d_edges, false, cap, part_counts);
 }
-
-int kq_emit_packed_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint64_t cap,
-                       uint64_t* part_counts) {
-    if (!h || !part_counts || n_parts < 1 || n_parts > h->map_count || n_parts >= NB_MAX || (!d_bases && len))
-        return fail(KQ_ERR_INVALID, "bad argument");
-    if (h->k > PART_MAX_K) return fail(KQ_ERR_INVALID, "packed 8-byte records need k <= %d (use kq_emit_partitioned_dev)", PART_MAX_K);
-    HIPC(hipSetDevice(h->device));
-    for (int i = 0; i < n_parts; ++i) part_counts[i] = 0;
-    if (len < (uint64_t)h->k) return KQ_OK;
-    if (len - h->k + 1 >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "an owner split handles fewer than 2^32 k-mer starts per call (got %llu): cut the batch", (unsigned long long)(len - h->k + 1));
-    if (cap < len - h->k + 1 || !d_recs) return fail(KQ_ERR_CAPACITY, "record buffer too small: need room for %llu records",
-                                                       (unsigned long long)(len - h->k + 1));
-    return owner_split(h, d_bases, len, n_parts, d_recs, nullptr, part_counts);
+int kq_emit_packed_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint64_t cap, uint64_t* part_counts) {
+    return owner_split(h, d_bases, len, n_parts, d_recs, nullptr, true, cap, part_counts);
 }
 
 // ---- multi-GPU exchange of 5-byte records (k <= 21) -------------------------------------------------
@@ -1805,29 +1797,33 @@ __global__ void k_bucket_meta(const unsigned long long* __restrict__ seg_off, ui
     const uint32_t lo = (uint32_t)(((uint64_t)p * 256 + n_parts - 1) / n_parts), hi = (uint32_t)(((uint64_t)(p + 1) * 256 + n_parts - 1) / n_parts);
     counts[j] = (b >= lo && b < hi) ? seg_off[b + 1] - seg_off[b] : 0ull;
 }
-int kq_emit_sharded_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint32_t* d_recs, uint8_t* d_aux, uint64_t cap,
+// `five`: 5-byte records (u32 + lockstep byte in d_aux), else 8-byte hash-remainder records (see below; d_aux = nullptr)
+static int emit_buckets(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint8_t* d_aux, bool five, uint64_t cap,
                         uint64_t* d_bucket_counts, uint64_t* part_counts) {
-    if (!h || !d_bucket_counts || n_parts < 1 || n_parts > 256 || (!d_bases && len))
-        return fail(KQ_ERR_INVALID, "bad argument");
-    if (h->k > (int)NARROW_MAX_K) return fail(KQ_ERR_INVALID, "5-byte records need k <= %u (use kq_emit_packed_dev)", NARROW_MAX_K);
+    if (!h || !d_bucket_counts || n_parts < 1 || n_parts > 256 || (!d_bases && len)) return fail(KQ_ERR_INVALID, "bad argument");
+    if (five && h->k > (int)NARROW_MAX_K) return fail(KQ_ERR_INVALID, "5-byte records need k <= %u (use kq_emit_packed_dev)", NARROW_MAX_K);
+    if (!five && h->k <= PART_MAX_K) return fail(KQ_ERR_INVALID, "8-byte hash-remainder records need k >= %d (use kq_emit_sharded_dev or kq_emit_packed_dev)", HI_K);
     HIPC(hipSetDevice(h->device));
     for (int i = 0; part_counts && i < n_parts; ++i) part_counts[i] = 0;
     const uint64_t n_groups = (uint64_t)n_parts << NARROW_CBITS;
     HIPC(hipMemsetAsync(d_bucket_counts, 0, n_groups * 8, h->stream));
     if (len < (uint64_t)h->k) { if (part_counts) HIPC(hipStreamSynchronize(h->stream)); return KQ_OK; }
     if (len - h->k + 1 >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "a bucket split handles fewer than 2^32 k-mer starts per call (got %llu): cut the batch", (unsigned long long)(len - h->k + 1));
-    if (cap < len - h->k + 1 || !d_recs || !d_aux) return fail(KQ_ERR_CAPACITY, "record buffers too small: need room for %llu records", (unsigned long long)(len - h->k + 1));
+    if (cap < len - h->k + 1 || !d_recs || (five && !d_aux)) return fail(KQ_ERR_CAPACITY, "record buffer%s too small: need room for %llu records", five ? "s" : "", (unsigned long long)(len - h->k + 1));
     const uint8_t* ab; uint64_t lead;
     aligned_view(d_bases, &ab, &lead);
     PartPlan p;
-    int rc = plan_alloc(h, &p, len, n_tiles_of(lead, len), 1u << NARROW_CBITS, true, n_groups);
+    // (P1 writes into the caller's buffers: the 8-byte form asks for no record scratch, the 5-byte form for its historical `len` records)
+    int rc = plan_alloc(h, &p, five ? len : 0, n_tiles_of(lead, len), 1u << NARROW_CBITS, true, n_groups);
     if (rc) return rc;
     // the bucket split of the single-GPU count IS the owner split: bucket = top 8 hash bits, whatever this rank's table
-    // looks like, and every part is a range of buckets -- P1 writes straight into the send buffers
+    // looks like (plan_cfg leaves the window of the sending handle out: every bucket is emitted), and every part is a range
+    // of buckets -- P1 writes straight into the send buffers
     PartCfg cfg = p.cfg;
     cfg.mode = 0; cfg.narrow = 1; cfg.n_coarse = 1u << NARROW_CBITS; cfg.sub_bits = 0; if (cfg.g_shift == 0) cfg.g_shift = 1;
     cfg.filt_lo = 0; cfg.filt_hi = cfg.map_count;
-    run_p1(h, &p, cfg, ab, lead, len, EmitRange{0, ~0ull}, (uint64_t*)d_recs, d_aux, AUX_IDX6);
+    rc = run_p1(h, &p, cfg, ab, lead, len, EmitRange{0, ~0ull}, d_recs, five ? d_aux : nullptr, AUX_IDX6);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_bucket_meta, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, h->stream, p.seg_off, (uint32_t)n_parts, (unsigned long long*)d_bucket_counts);
     HIPC(hipGetLastError());
     if (!part_counts) return KQ_OK;               // asynchronous: the caller takes the part sizes from the rows of d_bucket_counts
@@ -1837,80 +1833,15 @@ int kq_emit_sharded_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_p
     for (int i = 0; i < n_parts; ++i) part_counts[i] = off[part_first_bucket(i + 1, n_parts)] - off[part_first_bucket(i, n_parts)];
     return KQ_OK;
 }
-
-int kq_insert_sharded_dev(kq_handle* h, const uint32_t* d_recs, const uint8_t* d_aux, uint64_t n, int n_peers, const uint64_t* d_bucket_counts) {
-    if (!h || ((!d_recs || !d_aux) && n) || !d_bucket_counts || n_peers < 1 || n_peers > 256) return fail(KQ_ERR_INVALID, "bad argument");
-    if (h->k > (int)NARROW_MAX_K) return fail(KQ_ERR_INVALID, "5-byte records need k <= %u (use kq_insert_packed_dev)", NARROW_MAX_K);
+// receive side: the (peer, bucket) runs of all peers enter the table's bucket -> region levels
+static int insert_buckets(kq_handle* h, const uint64_t* d_recs, const uint8_t* d_aux, bool five, uint64_t n, int n_peers, const uint64_t* d_bucket_counts) {
+    if (!h || ((!d_recs || (five && !d_aux)) && n) || !d_bucket_counts || n_peers < 1 || n_peers > 256) return fail(KQ_ERR_INVALID, "bad argument");
+    if (five && h->k > (int)NARROW_MAX_K) return fail(KQ_ERR_INVALID, "5-byte records need k <= %u (use kq_insert_packed_dev)", NARROW_MAX_K);
+    if (!five && h->k <= PART_MAX_K) return fail(KQ_ERR_INVALID, "8-byte hash-remainder records need k >= %d (use kq_insert_sharded_dev or kq_insert_packed_dev)", HI_K);
     HIPC(hipSetDevice(h->device));
     if (!n) return KQ_OK;
     if (n >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "a partition pass handles fewer than 2^32 records (got %llu)", (unsigned long long)n);
-    int rc = reserve(h, n, n);
-    if (rc) return rc;
-    const uint32_t n_in = (uint32_t)n_peers << NARROW_CBITS;      // input segments: one run per (bucket, peer)
-    PartPlan p;
-    rc = plan_alloc(h, &p, n, 0, 1, true, n_in);
-    if (rc) return rc;
-    if (p.fmt != FMT_NARROW) return fail(KQ_ERR_INVALID, "the table is too small for 5-byte records (fewer than 2048 regions): use kq_insert_packed_dev");
-    // segment table of the received array (peer-major runs) in logical order (bucket-major)
-    HIPC(h->scratch.ensure((size_t)(3 * (n_in + 2)) * 8));
-    unsigned long long* start = h->scratch.as<unsigned long long>();
-    unsigned long long* seg_lo = start + n_in + 2;
-    unsigned long long* seg_hi = seg_lo + n_in + 2;
-    HIPC(hipMemcpyAsync(start, d_bucket_counts, (size_t)n_in * 8, hipMemcpyDeviceToDevice, h->stream));
-    hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, h->stream, start, (uint64_t)n_in, start + n_in);
-    hipLaunchKernelGGL(k_sharded_segments, dim3((n_in + 255) / 256), dim3(256), 0, h->stream, start, (const unsigned long long*)d_bucket_counts, (uint32_t)n_peers, seg_lo, seg_hi);
-    Dest dst{p.fmt, AUX_IDX6};
-    rc = dest_take(h, p, p.n_max, &dst); if (rc) return rc;
-    // the first level reads the received runs
-    const LevelIn runs{(const uint64_t*)d_recs, d_aux, seg_lo, seg_hi, n_in, (uint32_t)n_peers};
-    return submit(h, sort_to_regions(h, &p, runs, dst), dst);
-}
-
-// ---- multi-GPU exchange of 8-byte hash-remainder records (k = 29..32) -------------------------------
-// The same glue for FMT_TOP8: a record plus its bucket is the whole k-mer (top8_hash), tables of k >= HI_K have the bucket
-// geometry at every size, so ownership by bucket range makes P1 the owner split here too.  One u64 array crosses the link
-// (the 9-byte path: u64 key + edge byte in two arrays, hashed again by the receiver), and the receiver's levels start from
-// the (peer, bucket) runs.  kq_emit_partitioned_dev / kq_insert_records_dev remain for tables below 2048 regions.
-int kq_emit_sharded8_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint64_t cap,
-                         uint64_t* d_bucket_counts, uint64_t* part_counts) {
-    if (!h || !d_bucket_counts || n_parts < 1 || n_parts > 256 || (!d_bases && len))
-        return fail(KQ_ERR_INVALID, "bad argument");
-    if (h->k <= PART_MAX_K) return fail(KQ_ERR_INVALID, "8-byte hash-remainder records need k >= %d (use kq_emit_sharded_dev or kq_emit_packed_dev)", HI_K);
-    HIPC(hipSetDevice(h->device));
-    for (int i = 0; part_counts && i < n_parts; ++i) part_counts[i] = 0;
-    const uint64_t n_groups = (uint64_t)n_parts << NARROW_CBITS;
-    HIPC(hipMemsetAsync(d_bucket_counts, 0, n_groups * 8, h->stream));
-    if (len < (uint64_t)h->k) { if (part_counts) HIPC(hipStreamSynchronize(h->stream)); return KQ_OK; }
-    if (len - h->k + 1 >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "a bucket split handles fewer than 2^32 k-mer starts per call (got %llu): cut the batch", (unsigned long long)(len - h->k + 1));
-    if (cap < len - h->k + 1 || !d_recs) return fail(KQ_ERR_CAPACITY, "record buffer too small: need room for %llu records", (unsigned long long)(len - h->k + 1));
-    const uint8_t* ab; uint64_t lead;
-    aligned_view(d_bases, &ab, &lead);
-    PartPlan p;
-    int rc = plan_alloc(h, &p, 0, n_tiles_of(lead, len), 1u << NARROW_CBITS, true, n_groups);      // (P1 writes into the caller's buffer: no record scratch)
-    if (rc) return rc;
-    // bucket = top 8 hash bits whatever this rank's table looks like (plan_cfg leaves the window of the sending handle out:
-    // every bucket is emitted), and every part is a range of buckets
-    PartCfg cfg = p.cfg;
-    cfg.mode = 0; cfg.narrow = 1; cfg.n_coarse = 1u << NARROW_CBITS; cfg.sub_bits = 0; if (cfg.g_shift == 0) cfg.g_shift = 1;
-    cfg.filt_lo = 0; cfg.filt_hi = cfg.map_count;
-    run_p1(h, &p, cfg, ab, lead, len, EmitRange{0, ~0ull}, d_recs, nullptr, AUX_IDX6);
-    hipLaunchKernelGGL(k_bucket_meta, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, h->stream, p.seg_off, (uint32_t)n_parts, (unsigned long long*)d_bucket_counts);
-    HIPC(hipGetLastError());
-    if (!part_counts) return KQ_OK;               // asynchronous: the caller takes the part sizes from the rows of d_bucket_counts
-    std::vector<unsigned long long> off((size_t)(1u << NARROW_CBITS) + 1);
-    HIPC(hipMemcpyAsync(off.data(), p.seg_off, off.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPC(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n_parts; ++i) part_counts[i] = off[part_first_bucket(i + 1, n_parts)] - off[part_first_bucket(i, n_parts)];
-    return KQ_OK;
-}
-
-int kq_insert_sharded8_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n, int n_peers, const uint64_t* d_bucket_counts) {
-    if (!h || (!d_recs && n) || !d_bucket_counts || n_peers < 1 || n_peers > 256) return fail(KQ_ERR_INVALID, "bad argument");
-    if (h->k <= PART_MAX_K) return fail(KQ_ERR_INVALID, "8-byte hash-remainder records need k >= %d (use kq_insert_sharded_dev or kq_insert_packed_dev)", HI_K);
-    HIPC(hipSetDevice(h->device));
-    if (!n) return KQ_OK;
-    if (n >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "a partition pass handles fewer than 2^32 records (got %llu)", (unsigned long long)n);
-    {   // the format of the plan the table allows, before anything is reserved or grown for records it cannot take
+    if (!five) {   // the format of the plan the table allows, before anything is reserved or grown for records it cannot take
         PartCfg c; plan_cfg(h, &c, true);
         if (!c.narrow) return fail(KQ_ERR_INVALID, "the table has no hash-prefix bucket split for 8-byte hash-remainder records (fewer than 2048 regions): use kq_insert_records_dev");
     }
@@ -1920,7 +1851,8 @@ int kq_insert_sharded8_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n, int
     PartPlan p;
     rc = plan_alloc(h, &p, n, 0, 1, true, n_in);
     if (rc) return rc;
-    if (p.fmt != FMT_TOP8) return fail(KQ_ERR_INVALID, "the table has no hash-prefix bucket split for 8-byte hash-remainder records: use kq_insert_records_dev");
+    if (five && p.fmt != FMT_NARROW) return fail(KQ_ERR_INVALID, "the table is too small for 5-byte records (fewer than 2048 regions): use kq_insert_packed_dev");
+    if (!five && p.fmt != FMT_TOP8) return fail(KQ_ERR_INVALID, "the table has no hash-prefix bucket split for 8-byte hash-remainder records: use kq_insert_records_dev");
     // segment table of the received array (peer-major runs) in logical order (bucket-major)
     HIPC(h->scratch.ensure((size_t)(3 * (n_in + 2)) * 8));
     unsigned long long* start = h->scratch.as<unsigned long long>();
@@ -1933,8 +1865,26 @@ int kq_insert_sharded8_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n, int
     rc = dest_take(h, p, p.n_max, &dst); if (rc) return rc;
     // the first level reads the received runs; the table pass visits the window's regions only, so records of foreign buckets
     // are sorted and never applied
-    const LevelIn runs{d_recs, nullptr, seg_lo, seg_hi, n_in, (uint32_t)n_peers};
-    return submit(h, sort_to_regions(h, &p, runs, dst), dst);
+    const LevelIn runs{d_recs, five ? d_aux : nullptr, seg_lo, seg_hi, n_in, (uint32_t)n_peers};
+    return sort_and_submit(h, &p, runs, dst);
+}
+int kq_emit_sharded_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint32_t* d_recs, uint8_t* d_aux, uint64_t cap, uint64_t* d_bucket_counts, uint64_t* part_counts) {
+    return emit_buckets(h, d_bases, len, n_parts, (uint64_t*)d_recs, d_aux, true, cap, d_bucket_counts, part_counts);
+}
+int kq_insert_sharded_dev(kq_handle* h, const uint32_t* d_recs, const uint8_t* d_aux, uint64_t n, int n_peers, const uint64_t* d_bucket_counts) {
+    return insert_buckets(h, (const uint64_t*)d_recs, d_aux, true, n, n_peers, d_bucket_counts);
+}
+
+// ---- multi-GPU exchange of 8-byte hash-remainder records (k = 29..32) -------------------------------
+// The same glue for FMT_TOP8: a record plus its bucket is the whole k-mer (top8_hash), tables of k >= HI_K have the bucket
+// geometry at every size, so ownership by bucket range makes P1 the owner split here too.  One u64 array crosses the link
+// (the 9-byte path: u64 key + edge byte in two arrays, hashed again by the receiver), and the receiver's levels start from
+// the (peer, bucket) runs.  kq_emit_partitioned_dev / kq_insert_records_dev remain for tables below 2048 regions.
+int kq_emit_sharded8_dev(kq_handle* h, const char* d_bases, uint64_t len, int n_parts, uint64_t* d_recs, uint64_t cap, uint64_t* d_bucket_counts, uint64_t* part_counts) {
+    return emit_buckets(h, d_bases, len, n_parts, d_recs, nullptr, false, cap, d_bucket_counts, part_counts);
+}
+int kq_insert_sharded8_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n, int n_peers, const uint64_t* d_bucket_counts) {
+    return insert_buckets(h, d_recs, nullptr, false, n, n_peers, d_bucket_counts);
 }
 
 int kq_insert_packed_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n) {
@@ -2047,13 +1997,15 @@ static int lookup_partitioned(kq_handle* h, const uint8_t* ab, uint64_t lead, ui
     int rc = plan_sequence(h, &p, lead, len);
     if (rc) return rc;
     p.cfg.filt_lo = map_lo; p.cfg.filt_hi = map_hi;               // the reference's range filter, src/kreeq.cpp:150
-    run_p1(h, &p, p.cfg, ab, lead, len, er, p.recs1, p.a1(), AUX_IDX6);
-    const P3Set set = sort_to_regions(h, &p, own_segments(p, p.recs1, p.a1(), p.cfg.n_coarse), Dest{p.fmt, AUX_IDX6});      // in the scratch, never tight
+    rc = run_p1(h, &p, p.cfg, ab, lead, len, er, p.recs1, p.a1(), AUX_IDX6);
+    if (rc) return rc;
+    P3Set set;
+    rc = sort_to_regions(h, &p, own_segments(p, p.recs1, p.a1(), p.cfg.n_coarse), Dest{p.fmt, AUX_IDX6}, &set);      // in the scratch, never tight
+    if (rc) return rc;
     const uint32_t rps = (p.fmt == FMT_NARROW || p.fmt == FMT_TOP8) ? (uint32_t)(p.R >> NARROW_CBITS) : 1u;
-    const dim3 grid((unsigned)std::min<uint64_t>(p.R, 1u << 30)), block(P3_THREADS);
-#define KQ_LK(F) hipLaunchKernelGGL((k_lookup_regions<F>), grid, block, 0, h->stream, h->view(), set.recs, set.aux, set.base, rps, cov_cutoff, d_counters)
-    if (p.fmt == FMT_NARROW) KQ_LK(FMT_NARROW); else if (p.fmt == FMT_TOP8) KQ_LK(FMT_TOP8); else if (p.fmt == FMT_WIDE) KQ_LK(FMT_WIDE); else KQ_LK(FMT_PACK8);
-#undef KQ_LK
+    static const KernelRow<decltype(&k_lookup_regions<0>)> rows[] = {lkr<FMT_NARROW>(), lkr<FMT_TOP8>(), lkr<FMT_WIDE>(), lkr<FMT_PACK8>()};
+    rc = launch_row(rows, "k_lookup_regions", select_lookup(p.fmt), h, dim3((unsigned)std::min<uint64_t>(p.R, 1u << 30)), dim3(P3_THREADS), h->view(), set.recs, set.aux, set.base, rps, cov_cutoff, d_counters);
+    if (rc) return rc;
     HIPC(hipGetLastError());
     return KQ_OK;
 }
