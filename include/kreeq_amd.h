@@ -168,8 +168,10 @@ void* kq_get_stream(kq_handle* h);
  *                          the hash); bit 1 selects k_p1_scatter there too.  (8 is not assigned.)  Default 0. */
 /*   KQ_OPT_SUBGRAPH_BATCH  (on the DATABASE handle) searches per batch of kq_subgraph_best_first; 0 (default) = automatic: a scratch arena of
  *                          1 GiB divided by the bytes of one search's state block at the call's depth.  Results never depend on it. */
+/*   KQ_OPT_VARIANT_BATCH   searches per batch of kq_search_variants; 0 (default) = automatic: a scratch arena of 1 GiB divided by the
+ *                          bytes of one search's state block at the call's depth and span.  Results never depend on it. */
 enum { KQ_OPT_TRUST_CAPACITY = 1, KQ_OPT_COUNT_PATH = 2, KQ_OPT_SLICE_KMERS = 3, KQ_OPT_COUNT_MAP_RANGE = 4, KQ_OPT_PROFILE = 5,
-       KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13, KQ_OPT_SHARD_WINDOW = 14, KQ_OPT_SUBGRAPH_BATCH = 15,
+       KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13, KQ_OPT_SHARD_WINDOW = 14, KQ_OPT_SUBGRAPH_BATCH = 15, KQ_OPT_VARIANT_BATCH = 16,
        KQ_OPT_TEST_FAIL_PLAN = 100 /* failure-path tests only: the next partition plan of a count fails with KQ_ERR_NOMEM */ };
 int  kq_set_option(kq_handle* h, int option, int64_t value);
 int  kq_get_profile(kq_handle* h, char* buf, uint64_t cap);
@@ -358,6 +360,28 @@ int  kq_lookup_keys(kq_handle* h, const uint64_t* keys, uint64_t n, kq_entry* ou
  * above cov_cutoff, that does not lead to the k-mer the sequence continues with.  Only those positions need the host
  * search; everywhere else it returns at once without a variant.  flags has `len` bytes (0 where no k-mer starts). */
 int  kq_branch_scan(kq_handle* h, const char* bases, uint64_t len, uint32_t cov_cutoff, uint8_t* flags);
+
+/* The whole candidate-error search on the device (DBG::DBGtoVariants + searchVariants, src/variants.cpp:53-310, single map
+ * range): the pre-filter of kq_branch_scan, then one bounded graph search per flagged position -- one search per lane on a
+ * fixed-size state block (csrc/kq_variant_core.h), in batches of KQ_OPT_VARIANT_BATCH -- and the paths of all of them.
+ *   bases      what kq_branch_scan takes: host memory, segments = ACGT runs, len < 2^32 - 1
+ *   depth      --search-depth, 0 .. 253; max_span: --max-span, 0 .. 255 (the device limits; why 253: kq_variant_core.h).
+ *              max_span 0: the reference pops an empty queue; read as "the pop is skipped", the one target is k-mer c + k.
+ *   paths      one record per path, in ascending pos and, within one position, in destination order (the order of the
+ *              reference's `destinations`): pos = index in `bases` of the first base behind the source k-mer (c + k),
+ *              seg_start = index of the first base of that position's segment, seq + seq_off / seq_len = the path's bases
+ *              in upper case (not terminated), type = KQ_VAR_*, ref_len != 0 for KQ_VAR_COM only.
+ *   *n_paths, *n_seq   records and sequence bytes of the whole result; always set on KQ_OK and KQ_ERR_CAPACITY.
+ * paths == NULL or seq == NULL: only the two counts.  path_cap (records) or seq_cap (bytes) too small: KQ_ERR_CAPACITY with
+ * both counts set and nothing written; the searches are NOT kept, a repeat with larger buffers runs them again.  Null
+ * n_paths / n_seq, a windowed handle (KQ_OPT_BUCKET_WINDOW / KQ_OPT_SHARD_WINDOW), depth or max_span outside the limits, or
+ * len >= 2^32 - 1: KQ_ERR_INVALID before any device work.  len < k: KQ_OK, both counts zero.  Flushes pending records and
+ * synchronises.  Results do not depend on the batch size or on the launch geometry. */
+typedef struct { uint64_t pos, seg_start, seq_off; uint16_t seq_len, ref_len; uint8_t type, pad[3]; } kq_variant_path; /* 32 bytes */
+enum { KQ_VAR_SNV = 0, KQ_VAR_INS = 1, KQ_VAR_DEL = 2, KQ_VAR_COM = 3 };
+int  kq_search_variants(kq_handle* h, const char* bases, uint64_t len, int depth, int max_span, uint32_t cov_cutoff,
+                        kq_variant_path* paths, uint64_t path_cap, uint64_t* n_paths,
+                        char* seq, uint64_t seq_cap, uint64_t* n_seq);
 
 /* ---- union / database import-export --------------------------------------------------------- */
 

@@ -10,13 +10,16 @@ from . import build as _build
 
 ENTRY_DTYPE = np.dtype([("key", "<u8"), ("fw", "<u4", 4), ("bw", "<u4", 4), ("cov", "<u4"), ("hc", "<u4")])
 DBGBASE_DTYPE = np.dtype([("fw", "<u4"), ("bw", "<u4"), ("cov", "<u4"), ("isFw", "u1"), ("pad", "u1", 3)])
+VARIANT_PATH_DTYPE = np.dtype([("pos", "<u8"), ("seg_start", "<u8"), ("seq_off", "<u8"), ("seq_len", "<u2"), ("ref_len", "<u2"), ("type", "u1"), ("pad", "u1", 3)])      # kq_variant_path
+VAR_SNV, VAR_INS, VAR_DEL, VAR_COM = 0, 1, 2, 3      # KQ_VAR_*
+ERR_CAPACITY = -6                        # KQ_ERR_CAPACITY
 
 # every symbol include/kreeq_amd.h declares
 SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profile", "kq_set_stream", "kq_get_stream", "kq_sync", "kq_flush", "kq_get_info", "kq_last_error",
            "kq_abi_version", "kq_device_available", "kq_device_memory", "kq_count_batch", "kq_count_batch_dev", "kq_host_alloc", "kq_host_free", "kq_count_batch_async", "kq_host_wait", "kq_pack_bases", "kq_count_packed_dev", "kq_count_packed_async",
            "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
-           "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_lookup_keys", "kq_branch_scan", "kq_merge", "kq_import", "kq_export",
+           "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_lookup_keys", "kq_branch_scan", "kq_search_variants", "kq_merge", "kq_import", "kq_export",
            "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_best_first", "kq_subgraph_trim"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
@@ -127,6 +130,7 @@ def load():
     L.kq_lookup_sequence_dev.argtypes = [vp, vp, u64, u32, u16, u16, vp, vp]
     L.kq_lookup_keys.argtypes = [vp, vp, u64, vp]
     L.kq_branch_scan.argtypes = [vp, vp, u64, u32, vp]
+    L.kq_search_variants.argtypes = [vp, vp, u64, ci, ci, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
     L.kq_merge.argtypes = [vp, vp]
     L.kq_import.argtypes = [vp, vp, u64]
     L.kq_export.argtypes = [vp, u16, u16, vp, u64, C.POINTER(u64)]
@@ -204,7 +208,7 @@ class KreeqDB:
         """option: 'trust_capacity' | 'count_path' ('auto'|'direct'|'partitioned') | 'slice_kmers' | 'count_map_range' ((lo, hi)) |
         'kernel_set' (measurement only: mask of bits 1, 2, 4, 16, 32, 64, 128 -- KQ_OPT_KERNEL_SET in include/kreeq_amd.h; 32 / 64 = the last
         split level never / wherever possible with one workgroup per segment; 128 = the previous P1 scatter behind a map-range filter) | ..."""
-        opt = {"trust_capacity": 1, "count_path": 2, "slice_kmers": 3, "count_map_range": 4, "profile": 5, "lookup_path": 6, "merge_path": 7, "narrow_mid": 8, "pending_bytes": 9, "bucket_window": 10, "overlap": 11, "count_map_passes": 12, "kernel_set": 13, "shard_window": 14, "subgraph_batch": 15, "test_fail_plan": 100}[option]
+        opt = {"trust_capacity": 1, "count_path": 2, "slice_kmers": 3, "count_map_range": 4, "profile": 5, "lookup_path": 6, "merge_path": 7, "narrow_mid": 8, "pending_bytes": 9, "bucket_window": 10, "overlap": 11, "count_map_passes": 12, "kernel_set": 13, "shard_window": 14, "subgraph_batch": 15, "variant_batch": 16, "test_fail_plan": 100}[option]
         if option == "count_map_range":
             value = int(value[0]) | (int(value[1]) << 16)
         if option in ("count_path", "lookup_path", "merge_path"):
@@ -373,6 +377,29 @@ class KreeqDB:
         flags = np.zeros(len(buf), dtype=np.uint8)
         _check(load().kq_branch_scan(self._h, _p(buf), len(buf), cov_cutoff, _p(flags)))
         return flags
+
+    def search_variants_raw(self, bases: bytes, depth, max_span, cov_cutoff=0, path_cap=None, seq_cap=None):
+        """kq_search_variants as it is: path_cap None = the two counts only -> (return code, n_paths, n_seq, records, sequence bytes)"""
+        buf = np.frombuffer(bases, dtype=np.uint8)
+        n_paths, n_seq = C.c_uint64(0), C.c_uint64(0)
+        paths = np.zeros(max(path_cap, 1), dtype=VARIANT_PATH_DTYPE) if path_cap is not None else None
+        seq = np.zeros(max(seq_cap, 1), dtype=np.uint8) if path_cap is not None else None
+        rc = load().kq_search_variants(self._h, _p(buf) if len(buf) else None, len(buf), depth, max_span, cov_cutoff, _p(paths), path_cap or 0, C.byref(n_paths),
+                                       _p(seq), seq_cap or 0, C.byref(n_seq))
+        return rc, n_paths.value, n_seq.value, paths, seq
+
+    def search_variants(self, bases: bytes, depth, max_span, cov_cutoff=0):
+        """The candidate-error searches of `validate -o vcf` on the device (kq_search_variants): -> [(pos, seg_start, type,
+        ref_len, sequence)] in ascending pos, destination order within one position.  Modest buffers first; when they are
+        too small the call is repeated ONCE with the sizes it reported (the searches run again)."""
+        path_cap, seq_cap = 1 << 12, 1 << 16
+        rc, n_paths, n_seq, paths, seq = self.search_variants_raw(bases, depth, max_span, cov_cutoff, path_cap, seq_cap)
+        if rc == ERR_CAPACITY:
+            rc, n_paths, n_seq, paths, seq = self.search_variants_raw(bases, depth, max_span, cov_cutoff, n_paths, n_seq)
+        _check(rc)
+        text = seq.tobytes()
+        return [(int(p["pos"]), int(p["seg_start"]), int(p["type"]), int(p["ref_len"]), text[int(p["seq_off"]):int(p["seq_off"]) + int(p["seq_len"])].decode())
+                for p in paths[:n_paths]]
 
     # -- union / io
     def merge(self, other):

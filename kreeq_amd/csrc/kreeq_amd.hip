@@ -31,6 +31,7 @@ using namespace kq;
 #include "kq_fastx.h"
 #include "kq_dbimage.h"
 #include "kq_subgraph.h"
+#include "kq_variants.h"
 
 // ================================================================================================
 // host side
@@ -226,6 +227,7 @@ struct kq_handle {
                                          // changes its content: the address-keyed KQ_OPT_COUNT_MAP_PASSES cache must not see it
     bool test_fail_plan = false;         // KQ_OPT_TEST_FAIL_PLAN: the next partition plan fails with KQ_ERR_NOMEM (failure-path tests)
     DevMem hot;                          // k_count_regions' list of skewed regions
+    uint64_t var_batch = 0;              // KQ_OPT_VARIANT_BATCH: searches per batch of kq_search_variants, 0 = from the scratch budget
     uint64_t sg_batch = 0;               // KQ_OPT_SUBGRAPH_BATCH: searches per batch of kq_subgraph_best_first, 0 = from the scratch budget
 
     TableView view() const {
@@ -663,6 +665,9 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
         case KQ_OPT_SUBGRAPH_BATCH:
             if (value < 0) return fail(KQ_ERR_INVALID, "KQ_OPT_SUBGRAPH_BATCH must be 0 (automatic) or a number of searches");
             h->sg_batch = (uint64_t)value; return KQ_OK;
+        case KQ_OPT_VARIANT_BATCH:
+            if (value < 0) return fail(KQ_ERR_INVALID, "KQ_OPT_VARIANT_BATCH must be 0 (automatic) or a number of searches");
+            h->var_batch = (uint64_t)value; return KQ_OK;
         default: return fail(KQ_ERR_INVALID, "unknown option %d", option);
     }
 }
@@ -2112,6 +2117,133 @@ int kq_branch_scan(kq_handle* h, const char* bases, uint64_t len, uint32_t cov_c
     hipError_t e1 = hipMemcpyAsync(flags, d_flags, len, hipMemcpyDeviceToHost, h->stream);
     hipError_t e2 = hipStreamSynchronize(h->stream);
     if (e1 != hipSuccess || e2 != hipSuccess) return fail(KQ_ERR_HIP, "branch scan failed: %s", hipGetErrorString(e2 != hipSuccess ? e2 : e1));
+    return KQ_OK;
+}
+
+
+// Scratch budget of the candidate-error searches: every search of a batch owns one state block of kqvar::block_bytes(depth,
+// max_span) bytes (2.8 KB at depth 15 / span 32, 7.8 KB at depth 60 / span 20, 34.7 KB at the limits), so a batch is
+// VAR_ARENA_BYTES / block bytes searches (at least one, at most the flagged positions there are).  KQ_OPT_VARIANT_BATCH fixes
+// the number instead (tests).
+constexpr uint64_t VAR_ARENA_BYTES = 1ull << 30;
+
+// the ascending list of the i < len with word[i] != 0, through an exclusive prefix sum into rank -> *out (mem owns it), *n_out
+static int var_compact(kq_handle* h, DevScope& mem, const uint32_t* d_word, uint32_t* d_rank, uint64_t len, void* d_tmp, size_t tmp_bytes, uint32_t** out, uint64_t* n_out) {
+    hipStream_t st = h->stream;
+    HIPC(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_word, d_rank, (int64_t)len, st));
+    uint32_t last[2] = {0, 0};
+    HIPC(hipMemcpyAsync(&last[0], d_word + (len - 1), 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&last[1], d_rank + (len - 1), 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    *n_out = (uint64_t)last[0] + last[1];
+    if (mem.alloc((void**)out, (*n_out + 1) * 4) != hipSuccess) return fail(KQ_ERR_NOMEM, "no device memory for a list of %llu positions", (unsigned long long)*n_out);
+    if (*n_out) hipLaunchKernelGGL(k_var_scatter, dim3(grid_for(h, len, 256)), dim3(256), 0, st, d_word, (const uint32_t*)d_rank, len, *out, *n_out);
+    HIPC(hipGetLastError());
+    return KQ_OK;
+}
+
+int kq_search_variants(kq_handle* h, const char* bases, uint64_t len, int depth, int max_span, uint32_t cov_cutoff, kq_variant_path* paths, uint64_t path_cap,
+                       uint64_t* n_paths, char* seq, uint64_t seq_cap, uint64_t* n_seq) {
+    if (!h || (!bases && len) || !n_paths || !n_seq) return fail(KQ_ERR_INVALID, "null argument");
+    if (h->windowed) return fail(KQ_ERR_INVALID, "kq_search_variants does not take a windowed handle (KQ_OPT_BUCKET_WINDOW / KQ_OPT_SHARD_WINDOW)");
+    if (depth < 0 || depth > kqvar::MAX_DEPTH) return fail(KQ_ERR_INVALID, "search depth %d outside 0..%d", depth, kqvar::MAX_DEPTH);
+    if (max_span < 0 || max_span > kqvar::MAX_SPAN) return fail(KQ_ERR_INVALID, "max span %d outside 0..%d", max_span, kqvar::MAX_SPAN);
+    if (len >= 0xFFFFFFFFull) return fail(KQ_ERR_INVALID, "sequence batch of %llu bytes: search in batches below 2^32 - 1 bytes", (unsigned long long)len);
+    *n_paths = 0; *n_seq = 0;
+    HIPC(hipSetDevice(h->device));
+    if (len < (uint64_t)h->k) return KQ_OK;
+    int rc = flush_pending(h);
+    if (rc) return rc;
+    materialize(h);
+    void* d = nullptr;
+    rc = stage_in(h, bases, len, &d);
+    if (rc) return rc;
+    hipStream_t st = h->stream;
+    const uint8_t* d_text = (const uint8_t*)d;
+    const bool want_out = paths && seq;
+    DevScope mem;
+    // 1. the pre-filter, 2. the position list and the breaks
+    uint8_t* d_flags = nullptr;
+    uint32_t *d_word = nullptr, *d_rank = nullptr, *d_pos = nullptr, *d_breaks = nullptr;
+    void* d_tmp = nullptr;
+    size_t tmp_bytes = 0, tmp_bytes64 = 0;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_word, d_rank, (int64_t)len, st) != hipSuccess) return fail(KQ_ERR_HIP, "position scan setup failed");
+    if (mem.alloc((void**)&d_flags, len) != hipSuccess || mem.alloc((void**)&d_word, len * 4) != hipSuccess || mem.alloc((void**)&d_rank, len * 4) != hipSuccess ||
+        mem.alloc(&d_tmp, tmp_bytes) != hipSuccess)
+        return fail(KQ_ERR_NOMEM, "no device memory for the position scratch of %llu bases", (unsigned long long)len);
+    HIPC(hipMemsetAsync(d_flags, 0, len, st));
+    const uint8_t* ab; uint64_t lead;
+    aligned_view((const char*)d, &ab, &lead);
+    hipLaunchKernelGGL(k_branch_scan, dim3(grid_for(h, n_tiles_of(lead, len), 1, 32)), dim3(TILE_THREADS), 0, st, h->view(), ab, lead, len, h->k, cov_cutoff, d_flags);
+    hipLaunchKernelGGL(k_var_flag, dim3(grid_for(h, len, 256)), dim3(256), 0, st, (const uint8_t*)d_flags, len, d_word);
+    HIPC(hipGetLastError());
+    uint64_t n_pos = 0, n_breaks = 0;
+    rc = var_compact(h, mem, d_word, d_rank, len, d_tmp, tmp_bytes, &d_pos, &n_pos);
+    if (rc) return rc;
+    if (!n_pos) return KQ_OK;
+    hipLaunchKernelGGL(k_sg_invalid, dim3(grid_for(h, len, 256)), dim3(256), 0, st, d_text, len, d_word);
+    rc = var_compact(h, mem, d_word, d_rank, len, d_tmp, tmp_bytes, &d_breaks, &n_breaks);
+    if (rc) return rc;
+    HIPC(hipStreamSynchronize(st));                                  // the scatter above reads what is released here
+    mem.release(d_flags); mem.release(d_word); mem.release(d_rank); mem.release(d_tmp);
+    d_tmp = nullptr;
+    // 3. the searches, batch by batch
+    const uint64_t block_bytes = kqvar::block_bytes(depth, max_span);
+    const uint64_t batch = std::min<uint64_t>(n_pos, h->var_batch ? h->var_batch : std::max<uint64_t>(1, VAR_ARENA_BYTES / block_bytes));
+    // no result is larger than this, whatever the caller offers
+    const uint64_t most_paths = n_pos * kqvar::dest_bound(depth), most_seq = most_paths * (uint64_t)std::max(std::max(max_span, depth + 1), 1);
+    const uint64_t cap_paths = std::min(path_cap, most_paths), cap_seq = std::min(seq_cap, most_seq);
+    uint8_t* d_arena = nullptr;
+    unsigned long long *d_cnt = nullptr, *d_off = nullptr;               // [0, batch): paths, [batch, 2 batch): sequence bytes
+    VarState* d_state = nullptr;
+    kq_variant_path* d_paths = nullptr;
+    char* d_seq = nullptr;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes64, d_cnt, d_off, (int64_t)batch, st) != hipSuccess) return fail(KQ_ERR_HIP, "offset scan setup failed");
+    if (mem.alloc((void**)&d_state, sizeof(VarState)) != hipSuccess || mem.alloc((void**)&d_cnt, 2 * batch * 8) != hipSuccess || mem.alloc((void**)&d_off, 2 * batch * 8) != hipSuccess ||
+        mem.alloc(&d_tmp, tmp_bytes64) != hipSuccess)
+        return fail(KQ_ERR_NOMEM, "no device memory");
+    if (mem.alloc((void**)&d_arena, batch * block_bytes) != hipSuccess)
+        return fail(KQ_ERR_NOMEM, "no device memory for the state blocks of %llu searches of depth %d, span %d", (unsigned long long)batch, depth, max_span);
+    if (want_out && (mem.alloc((void**)&d_paths, cap_paths * sizeof(kq_variant_path)) != hipSuccess || mem.alloc((void**)&d_seq, cap_seq) != hipSuccess))
+        return fail(KQ_ERR_NOMEM, "no device memory for %llu paths and %llu sequence bytes", (unsigned long long)cap_paths, (unsigned long long)cap_seq);
+    uint64_t tot_paths = 0, tot_seq = 0;
+    bool emit = want_out;                                                // until the totals pass a cap: then the rest is only counted
+    VarState state{};
+    for (uint64_t lo = 0; lo < n_pos; lo += batch) {
+        const uint64_t n = std::min(batch, n_pos - lo);
+        HIPC(hipMemsetAsync(d_arena, 0xFF, n * block_bytes, st));       // the node indexes: every slot free (the rest of a block is written before it is read)
+        HIPC(hipMemsetAsync(d_state, 0, sizeof(VarState), st));
+        hipLaunchKernelGGL(k_var_search, dim3(grid_for(h, n, 256)), dim3(256), 0, st, h->view(), d_text, len, (const uint32_t*)(d_pos + lo), n, (const uint32_t*)d_breaks,
+                           (uint32_t)n_breaks, depth, max_span, cov_cutoff, d_arena, block_bytes, d_cnt, d_cnt + batch, d_state);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(&state, d_state, sizeof state, hipMemcpyDeviceToHost, st));      // only the batch's totals and the error mask return to the host
+        HIPC(hipStreamSynchronize(st));
+        if (state.err) return fail(KQ_ERR_HIP, "candidate-error search: a search left its state block's bounds (error mask %u)", state.err);      // cannot happen: kq_variant_core.h
+        const uint64_t base_paths = tot_paths, base_seq = tot_seq;
+        tot_paths += state.n_paths; tot_seq += state.n_seq;
+        if (tot_paths > cap_paths || tot_seq > cap_seq) emit = false;
+        if (!emit || !state.n_paths) continue;
+        // 4. where every search of the batch writes, then the records and bases themselves
+        HIPC(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes64, d_cnt, d_off, (int64_t)n, st));
+        HIPC(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes64, d_cnt + batch, d_off + batch, (int64_t)n, st));
+        hipLaunchKernelGGL(k_var_emit, dim3(grid_for(h, n, 256)), dim3(256), 0, st, h->view(), d_text, len, (const uint32_t*)(d_pos + lo), n, (const uint32_t*)d_breaks,
+                           (uint32_t)n_breaks, depth, max_span, d_arena, block_bytes, (const unsigned long long*)d_off, (const unsigned long long*)(d_off + batch), base_paths,
+                           base_seq, d_paths, cap_paths, d_seq, cap_seq, d_state);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(&state, d_state, sizeof state, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        if (state.err) return fail(KQ_ERR_HIP, "candidate-error search: a path left its bounds (error mask %u)", state.err);      // cannot happen: the totals fit
+    }
+    *n_paths = tot_paths; *n_seq = tot_seq;
+    if (!want_out) return KQ_OK;
+    if (tot_paths > path_cap || tot_seq > seq_cap)
+        return fail(KQ_ERR_CAPACITY, "%llu paths with %llu sequence bytes: the buffers hold %llu and %llu", (unsigned long long)tot_paths, (unsigned long long)tot_seq,
+                    (unsigned long long)path_cap, (unsigned long long)seq_cap);
+    // 5. copy out
+    hipError_t e1 = tot_paths ? hipMemcpyAsync(paths, d_paths, tot_paths * sizeof(kq_variant_path), hipMemcpyDeviceToHost, st) : hipSuccess;
+    hipError_t e2 = tot_seq ? hipMemcpyAsync(seq, d_seq, tot_seq, hipMemcpyDeviceToHost, st) : hipSuccess;
+    hipError_t e3 = hipStreamSynchronize(st);
+    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(KQ_ERR_HIP, "candidate-error search: copy out failed: %s", hipGetErrorString(e3 != hipSuccess ? e3 : e1 != hipSuccess ? e1 : e2));
     return KQ_OK;
 }
 

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstdlib>
 #include <deque>
 #include <stdexcept>
 #include <thread>
@@ -146,11 +147,83 @@ GraphSource graph_of_handle(kq_handle* h) {
     g.lookup = [h](const std::vector<uint64_t>& want, std::vector<kq_entry>& got) {
         if (kq_lookup_keys(h, want.data(), want.size(), got.data()) != KQ_OK) throw std::runtime_error(std::string("Error: ") + kq_last_error());
     };
+    g.resident = h;
     return g;
 }
 
+namespace {
+
+// KQ_VCF_DEVICE=1: the candidate-error searches run on the GPU, one per lane (kq_search_variants); off by default
+bool vcf_device() { static const bool on = [] { const char* e = getenv("KQ_VCF_DEVICE"); return e && atoi(e) != 0; }(); return on; }
+
+// The searches of seqs[lo, hi) in one kq_search_variants call over their joined text -> sites appended to `out`
+void device_call(kq_handle* h, const std::vector<SeqRecord>& seqs, size_t lo, size_t hi, int kmer_depth, int max_span, uint32_t cov_cutoff,
+                 std::vector<kq_variant_path>& paths, std::vector<char>& bases, std::vector<VariantSite>& out, uint64_t& n_calls) {
+    std::string joined;
+    std::vector<uint64_t> offset;
+    for (size_t si = lo; si < hi; ++si) { offset.push_back(joined.size()); joined += seqs[si].seq; joined.push_back('\n'); }
+    uint64_t n_paths = 0, n_seq = 0;
+    int rc = kq_search_variants(h, joined.data(), joined.size(), kmer_depth, max_span, cov_cutoff, paths.data(), paths.size(), &n_paths, bases.data(), bases.size(), &n_seq);
+    ++n_calls;
+    if (rc == KQ_ERR_CAPACITY) {                                         // once more with the sizes it reported (the searches run again)
+        paths.resize((size_t)n_paths); bases.resize((size_t)n_seq);
+        rc = kq_search_variants(h, joined.data(), joined.size(), kmer_depth, max_span, cov_cutoff, paths.data(), paths.size(), &n_paths, bases.data(), bases.size(), &n_seq);
+        ++n_calls;
+    }
+    if (rc != KQ_OK) throw std::runtime_error(std::string("Error: ") + kq_last_error());
+    for (uint64_t i = 0; i < n_paths; ++i) {
+        const kq_variant_path& r = paths[(size_t)i];
+        if (i == 0 || r.pos != paths[(size_t)i - 1].pos) {               // the paths of one position are one site
+            const size_t si = (size_t)(std::upper_bound(offset.begin(), offset.end(), r.seg_start) - offset.begin()) - 1;
+            VariantSite v;
+            v.seq_index = lo + si;
+            v.seg_start = r.seg_start - offset[si];
+            out.push_back(std::move(v));
+        }
+        DbgPath p;
+        p.type = (VariantType)r.type;                                    // KQ_VAR_* == VariantType
+        p.pos = r.pos - r.seg_start;
+        p.sequence.assign(bases.data() + r.seq_off, r.seq_len);
+        p.ref_len = r.ref_len;
+        out.back().paths.push_back(std::move(p));
+    }
+}
+
+std::vector<VariantSite> find_candidate_errors_device(kq_handle* h, const std::vector<SeqRecord>& seqs, int kmer_depth, int max_span, uint32_t cov_cutoff,
+                                                      const std::function<void(const std::string&)>& log) {
+    static_assert((int)VAR_SNV == KQ_VAR_SNV && (int)VAR_INS == KQ_VAR_INS && (int)VAR_DEL == KQ_VAR_DEL && (int)VAR_COM == KQ_VAR_COM, "path types");
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
+    std::vector<VariantSite> out;
+    std::vector<kq_variant_path> paths(1 << 16);                         // modest caps; a call that needs more says how much
+    std::vector<char> bases(1 << 22);
+    uint64_t n_calls = 0, n_records = 0;
+    for (size_t lo = 0; lo < seqs.size();) {                             // whole sequences, at most kVcfDeviceCallBytes of joined text per call
+        size_t hi = lo;
+        uint64_t bytes = 0;
+        while (hi < seqs.size() && (hi == lo || bytes + seqs[hi].seq.size() + 1 <= kVcfDeviceCallBytes)) { bytes += seqs[hi].seq.size() + 1; ++hi; }
+        device_call(h, seqs, lo, hi, kmer_depth, max_span, cov_cutoff, paths, bases, out, n_calls);
+        lo = hi;
+    }
+    for (auto& v : out) n_records += v.paths.size();
+    if (log) log("Device searches: " + std::to_string(n_calls) + " calls, " + std::to_string(out.size()) + " sites, " + std::to_string(n_records) + " paths; " +
+                 std::to_string(now() - t0) + " s");
+    return out;
+}
+
+}  // namespace
+
 std::vector<VariantSite> find_candidate_errors(const GraphSource& g, int k, const std::vector<SeqRecord>& seqs, int kmer_depth, int max_span,
                                                uint32_t cov_cutoff, const std::function<void(const std::string&)>& log) {
+    if (vcf_device()) {
+        bool fits = g.resident && kmer_depth >= 0 && kmer_depth <= kVcfDeviceMaxDepth && max_span >= kVcfDeviceMinSpan && max_span <= kVcfDeviceMaxSpan;
+        for (auto& r : seqs) fits = fits && r.seq.size() + 1 <= kVcfDeviceCallBytes;
+        if (fits) {
+            if (log) log("candidate-error search ran as the device search");
+            return find_candidate_errors_device(g.resident, seqs, kmer_depth, max_span, cov_cutoff, log);
+        }
+    }
+    if (log) log("candidate-error search ran as the host search");
     // 1. device pre-filter over the whole assembly (sequences joined by a non-base byte)
     std::string joined;
     std::vector<uint64_t> offset;

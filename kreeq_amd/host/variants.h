@@ -27,10 +27,18 @@ struct VariantSite { size_t seq_index = 0; uint64_t seg_start = 0; std::vector<D
 struct GraphSource {
     std::function<void(const std::string& joined, uint32_t cov_cutoff, std::vector<uint8_t>& flags)> branch_scan;
     std::function<void(const std::vector<uint64_t>& want, std::vector<kq_entry>& got)> lookup;
+    kq_handle* resident = nullptr;                              // the one table that holds the whole graph (graph_of_handle); null under map-range passes
 };
 GraphSource graph_of_handle(kq_handle* h);
 
-// DBG::correctSequences over all sequences: device pre-filter + host searches with batched device lookups
+// The device limits of kq_search_variants as the CLI uses them.  max_span 0 stays with the host search: the reference pops an
+// empty queue there, and the host search (no target) and the device search (the pop skipped: one target, k-mer c + k) differ.
+constexpr int kVcfDeviceMaxDepth = 253, kVcfDeviceMinSpan = 1, kVcfDeviceMaxSpan = 255;
+constexpr uint64_t kVcfDeviceCallBytes = 1ull << 30;            // joined text per kq_search_variants call
+
+// DBG::correctSequences over all sequences: device pre-filter + host searches with batched device lookups.  With KQ_VCF_DEVICE=1
+// (off by default), a resident table, depth and span inside the device limits and no sequence above kVcfDeviceCallBytes, the
+// searches run on the device instead (kq_search_variants), whole sequences grouped into calls; the sites are the same.
 std::vector<VariantSite> find_candidate_errors(const GraphSource& g, int k, const std::vector<SeqRecord>& seqs, int kmer_depth, int max_span,
                                                uint32_t cov_cutoff, const std::function<void(const std::string&)>& log = nullptr);
 inline std::vector<VariantSite> find_candidate_errors(kq_handle* h, int k, const std::vector<SeqRecord>& seqs, int kmer_depth, int max_span,

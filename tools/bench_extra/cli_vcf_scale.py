@@ -26,13 +26,26 @@ def make(scale, d):
             f.write(b">contig%d\n" % c + lut[a[c * 30000:(c + 1) * 30000]].tobytes() + b"\n")
     return fa, fq
 
+# --device: every scale once with the host search and once with KQ_VCF_DEVICE=1 (the device search), in that order, and the
+# two VCFs must be the same bytes; without it: the host search twice, as before
+args = [a for a in sys.argv[1:] if a != "--device"]
+modes = [("host", "0"), ("device", "1")] if "--device" in sys.argv[1:] else [("host", "0"), ("host", "0")]
 d = "/tmp/vcfscale"; os.makedirs(d, exist_ok=True)
-for scale in [int(x) for x in (sys.argv[1:] or ["1", "10", "100"])]:
+if "--print-cmd" in args:                                               # --print-cmd SCALE: write that scale's inputs, print the CLI command (for a profiler) and stop
+    fa, fq = make(int(args[args.index("--print-cmd") + 1]), d)
+    print(" ".join([build.CLI, "validate", "-f", fa, "-r", fq, "-k", "31", "-o", "vcf", "--search-depth", "40", "--max-span", "16"]))
+    sys.exit(0)
+for scale in [int(x) for x in (args or ["1", "10", "100"])]:
     fa, fq = make(scale, d)
-    for rep in range(2):
+    outs = []
+    for name, flag in modes:
         t0 = time.perf_counter()
-        p = subprocess.run([build.CLI, "validate", "-f", fa, "-r", fq, "-k", "31", "-o", "vcf", "--search-depth", "40", "--max-span", "16", "--verbose"], capture_output=True, text=True)
+        p = subprocess.run([build.CLI, "validate", "-f", fa, "-r", fq, "-k", "31", "-o", "vcf", "--search-depth", "40", "--max-span", "16", "--verbose"], capture_output=True, text=True,
+                           env=dict(os.environ, KQ_VCF_DEVICE=flag))
         dt = time.perf_counter() - t0
         assert p.returncode == 0, p.stderr[-2000:]
+        outs.append(p.stdout)
         n = sum(1 for l in p.stdout.split("\n") if l.startswith("contig"))
-        print(f"scale {scale}: wall {dt:.2f} s, {n} VCF records;", " | ".join(l.strip() for l in p.stderr.split("\n") if "s]" in l or "Candidate" in l)[:2500], flush=True)
+        print(f"scale {scale} {name} search: wall {dt:.2f} s, {n} VCF records;", " | ".join(l.strip() for l in p.stderr.split("\n") if "s]" in l or "Candidate" in l)[:2500], flush=True)
+    assert outs[0] == outs[1], f"scale {scale}: the VCFs of the two runs differ"
+    print(f"scale {scale}: identical VCF in both runs", flush=True)
