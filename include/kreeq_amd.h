@@ -347,6 +347,52 @@ int  kq_lookup_sequence_dev(kq_handle* h, const char* d_bases, uint64_t len, uin
                             uint16_t map_lo, uint16_t map_hi, kq_dbgbase* d_per_base,
                             uint64_t* d_counters);
 
+/* ---- per-base tables (.kwig / .bkwig / .bed / .csvtable; src/kreeq-output.cpp:138-399, src/decompressor.cpp:493-585) ------ */
+
+/* Device memory for callers that do not link the HIP runtime (the CLI): a block on the handle's GPU, zero-filled on the
+ * handle's stream, owned by the handle (kq_destroy frees what kq_dev_free has not; NULL when there is no memory).
+ * kq_dev_free waits for the device.  kq_copy_async: dst <- src, `bytes` bytes,
+ * asynchronous on the handle's stream (host memory should come from kq_host_alloc); kq_sync() waits for it. */
+enum { KQ_COPY_TO_DEVICE = 1, KQ_COPY_TO_HOST = 2 };
+void* kq_dev_alloc(kq_handle* h, uint64_t bytes);
+void  kq_dev_free(kq_handle* h, void* p);
+int   kq_copy_async(kq_handle* h, void* dst, const void* src, uint64_t bytes, int kind);
+
+/* The payload of a .bkwig from the per-base array of a lookup (src/kreeq-output.cpp:357-399): the entries of the listed
+ * segments (seg_start[s] = index of the segment's first entry in d_per_base, seg_len[s] entries; host arrays), in order, as
+ * ORIENTED u32 triples: cov, isFw ? fw : bw, isFw ? bw : fw.  d_triples receives sum(seg_len) x 12 bytes; what lies between
+ * the segments (separators, N runs) is dropped.  The kernel is enqueued on the handle's stream and the call does not wait
+ * for it; it does wait for what the stream held before (the segment lists are copied first).  KQ_ERR_INVALID for null
+ * pointers or 2^32 - 1 segments and more; no segment or only empty ones: KQ_OK without device work. */
+int  kq_per_base_triples_dev(kq_handle* h, const kq_dbgbase* d_per_base, const uint64_t* seg_start, const uint64_t* seg_len,
+                             uint64_t n_segs, uint32_t* d_triples);
+
+/* Triples -> decimal text, formatted on the device.  A call formats PIECES in order; piece p covers the triples
+ * first .. first + n - 1 and the coordinates abs_pos .. abs_pos + n - 1, and names + name_off / name_len is its sequence name.
+ *   KQ_TABLE_KWIG  per piece: when flags has KQ_TABLE_SEG_HEADER the line "fixedStep chrom=<name> start=<abs_pos> step=1\n",
+ *                  then "c,f,b\n" per position (src/kreeq-output.cpp:275-281)
+ *   KQ_TABLE_BED   column separator '\t', entry separator ':'        KQ_TABLE_CSV   both ','
+ *                  the line of position i is <name><col><abs_pos + i><col>W(cov)<col>W(fw)<col>W(bw)\n, W(x) = the k values
+ *                  of column x at positions i - k + 1 .. i, oldest first, joined by the entry separator; k = the handle's k
+ *                  (src/kreeq-output.cpp:176-219, src/decompressor.cpp:534-579).  The n_ctx triples before `first` are the
+ *                  window's history (a segment cut into pieces: n_ctx = min(cut, k - 1)); a position before that reads as 0.
+ *                  A window never reads across a piece boundary beyond n_ctx.  (KQ_TABLE_KWIG ignores n_ctx beyond checking it.)
+ * The output is the concatenated text.  *n_out = its size, always set on KQ_OK and KQ_ERR_CAPACITY.  out == NULL: the size
+ * query.  cap < size: KQ_ERR_CAPACITY, nothing is written.  Offsets are 64-bit; a call takes fewer than 2^32 lines.
+ * KQ_ERR_INVALID before any device work: null pointers (h, n_out; segs with n_segs, triples with n_triples, names with
+ * names_len), an unknown format, n_ctx > k - 1 or n_ctx > first, first + n > n_triples, a name outside `names` or longer than
+ * 65535 bytes, 2^32 lines or more.  No piece or no line: KQ_OK, *n_out = 0.  The bytes do not depend on the launch geometry,
+ * and cutting a segment into pieces (the first with the header flag, the others with their n_ctx) gives the bytes of the
+ * whole segment.  kq_format_table_dev takes device `d_triples` / `d_out`, kq_format_table host memory; `segs` and `names` are
+ * host memory in both.  Both synchronise. */
+typedef struct { uint64_t first, n, abs_pos; uint32_t name_off, name_len, n_ctx, flags; } kq_table_seg;      /* 40 bytes */
+enum { KQ_TABLE_SEG_HEADER = 1 };
+enum { KQ_TABLE_KWIG = 1, KQ_TABLE_BED = 2, KQ_TABLE_CSV = 3 };
+int  kq_format_table_dev(kq_handle* h, int format, const uint32_t* d_triples, uint64_t n_triples, const kq_table_seg* segs, uint64_t n_segs,
+                         const char* names, uint64_t names_len, char* d_out, uint64_t cap, uint64_t* n_out);
+int  kq_format_table(kq_handle* h, int format, const uint32_t* triples, uint64_t n_triples, const kq_table_seg* segs, uint64_t n_segs,
+                     const char* names, uint64_t names_len, char* out, uint64_t cap, uint64_t* n_out);
+
 /* ---- candidate-error search support (DBG::correctSequences, src/variants.cpp) --------------------------------- */
 
 /* Batched map->find(key) (src/variants.cpp:118-131, :203-206; src/kreeq.cpp:152-166 for the 32-bit tier): the logical

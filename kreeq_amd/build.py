@@ -2,6 +2,7 @@
 
   kreeq_amd/lib/libkreeq_amd.so   HIP kernels + C ABI (include/kreeq_amd.h), gfx950 only
   kreeq_amd/bin/kreeq             host CLI clone (validate / union / subgraph), links the library above
+  kreeq_amd/bin/kreeq-decompressor  reader of .bkwig files (inflate / lookup), links the library above
 """
 import os
 import shutil
@@ -14,8 +15,10 @@ CLI = os.path.join(PKG, "bin", "kreeq")
 HOSTLIB = os.path.join(PKG, "lib", "libkreeq_host.so")       # .kreeq database files for the multi-GPU driver (no GPU code)
 
 HIP_SOURCES = [os.path.join(PKG, "csrc", "kreeq_amd.hip")]
-HIP_DEPS = HIP_SOURCES + [os.path.join(PKG, "csrc", f) for f in ("kq_device.h", "kq_partition.h", "kq_kernels.h", "kq_fastx.h", "kq_dbimage.h", "kq_dbimage_host.h", "kq_mem_host.h", "kq_roff_host.h", "kq_seg_gate_host.h", "kq_select_host.h", "kq_formats.h", "kq_subgraph.h", "kq_bestfirst_core.h", "kq_nodequeue_core.h", "kq_variant_core.h", "kq_variants.h")] + [os.path.join(ROOT, "include", "kreeq_amd.h")]
+HIP_DEPS = HIP_SOURCES + [os.path.join(PKG, "csrc", f) for f in ("kq_device.h", "kq_partition.h", "kq_kernels.h", "kq_fastx.h", "kq_dbimage.h", "kq_dbimage_host.h", "kq_mem_host.h", "kq_roff_host.h", "kq_seg_gate_host.h", "kq_select_host.h", "kq_formats.h", "kq_subgraph.h", "kq_bestfirst_core.h", "kq_nodequeue_core.h", "kq_variant_core.h", "kq_variants.h", "kq_table_core.h", "kq_table.h")] + [os.path.join(ROOT, "include", "kreeq_amd.h")]
 HOST_DIR = os.path.join(PKG, "host")
+DECOMPRESSOR_DIR = os.path.join(HOST_DIR, "decompressor")      # a directory of its own: host_sources() takes every host/*.cpp into the kreeq binary
+DECOMPRESSOR = os.path.join(PKG, "bin", "kreeq-decompressor")
 
 
 def _stale(target, deps):
@@ -78,7 +81,21 @@ def build_cli(force=False, verbose=False):
     return CLI
 
 
+def build_decompressor(force=False, verbose=False):
+    srcs = [os.path.join(DECOMPRESSOR_DIR, "main.cpp")]
+    deps = srcs + [os.path.join(HOST_DIR, "bkwig_index.h"), os.path.join(PKG, "csrc", "kq_table_core.h"), os.path.join(ROOT, "include", "kreeq_amd.h"), LIB]
+    if force or _stale(DECOMPRESSOR, deps):
+        os.makedirs(os.path.dirname(DECOMPRESSOR), exist_ok=True)
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-o", DECOMPRESSOR] + srcs + \
+              ["-L", os.path.dirname(LIB), "-lkreeq_amd", "-Wl,-rpath,$ORIGIN/../lib"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return DECOMPRESSOR
+
+
 def build_all(force=False, verbose=False):
     build_lib(force, verbose)
     build_cli(force, verbose)
+    build_decompressor(force, verbose)
     build_hostlib(force, verbose)

@@ -19,10 +19,13 @@ SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profi
            "kq_abi_version", "kq_device_available", "kq_device_memory", "kq_count_batch", "kq_count_batch_dev", "kq_host_alloc", "kq_host_free", "kq_count_batch_async", "kq_host_wait", "kq_pack_bases", "kq_count_packed_dev", "kq_count_packed_async",
            "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
-           "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_lookup_keys", "kq_branch_scan", "kq_search_variants", "kq_merge", "kq_import", "kq_export",
+           "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_dev_alloc", "kq_dev_free", "kq_copy_async", "kq_per_base_triples_dev", "kq_format_table_dev", "kq_format_table", "kq_lookup_keys", "kq_branch_scan", "kq_search_variants", "kq_merge", "kq_import", "kq_export",
            "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_best_first", "kq_subgraph_trim"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
+TABLE_KWIG, TABLE_BED, TABLE_CSV = 1, 2, 3      # KQ_TABLE_*
+TABLE_SEG_HEADER = 1                     # KQ_TABLE_SEG_HEADER
+TABLE_SEG_DTYPE = np.dtype([("first", "<u8"), ("n", "<u8"), ("abs_pos", "<u8"), ("name_off", "<u4"), ("name_len", "<u4"), ("n_ctx", "<u4"), ("flags", "<u4")])      # kq_table_seg
 SUBGRAPH_NO_REFERENCE = 1                # KQ_SUBGRAPH_NO_REFERENCE
 
 
@@ -128,6 +131,14 @@ def load():
     L.kq_histogram.argtypes = [vp, vp, vp, u64, C.POINTER(u64)]
     L.kq_lookup_sequence.argtypes = [vp, vp, u64, u32, u16, u16, vp, vp]
     L.kq_lookup_sequence_dev.argtypes = [vp, vp, u64, u32, u16, u16, vp, vp]
+    L.kq_dev_alloc.argtypes = [vp, u64]
+    L.kq_dev_alloc.restype = vp
+    L.kq_dev_free.argtypes = [vp, vp]
+    L.kq_dev_free.restype = None
+    L.kq_copy_async.argtypes = [vp, vp, vp, u64, ci]
+    L.kq_per_base_triples_dev.argtypes = [vp, vp, vp, vp, u64, vp]
+    L.kq_format_table_dev.argtypes = [vp, ci, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]
+    L.kq_format_table.argtypes = [vp, ci, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]
     L.kq_lookup_keys.argtypes = [vp, vp, u64, vp]
     L.kq_branch_scan.argtypes = [vp, vp, u64, u32, vp]
     L.kq_search_variants.argtypes = [vp, vp, u64, ci, ci, u32, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
@@ -365,6 +376,35 @@ class KreeqDB:
             map_hi = self.map_count
         _check(load().kq_lookup_sequence_dev(self._h, C.c_void_p(bases_ptr), n, cov_cutoff, map_lo, map_hi,
                                              C.c_void_p(per_base_ptr) if per_base_ptr else None, C.c_void_p(counters_ptr)))
+
+    # -- per-base tables
+    def per_base_triples_dev(self, per_base_ptr, segments, triples_ptr):
+        """segments = [(start, len)] inside the device per-base array -> their oriented triples at triples_ptr (device, 12 bytes
+        per position); asynchronous on the handle's stream"""
+        start = np.array([s for s, _ in segments], dtype=np.uint64)
+        length = np.array([n for _, n in segments], dtype=np.uint64)
+        _check(load().kq_per_base_triples_dev(self._h, C.c_void_p(per_base_ptr), _p(start), _p(length), len(segments), C.c_void_p(triples_ptr)))
+
+    def format_table_raw(self, fmt, triples, n_triples, segs, n_segs, names, names_len, out, cap, n_out=True, dev=False):
+        """kq_format_table(_dev) as it is; every pointer a ctypes pointer / address or None -> (return code, *n_out)"""
+        n = C.c_uint64(0)
+        f = load().kq_format_table_dev if dev else load().kq_format_table
+        rc = f(self._h, fmt, triples, n_triples, segs, n_segs, names, names_len, out, cap, C.byref(n) if n_out else None)
+        return rc, n.value
+
+    def format_table(self, fmt, triples, segs, names: bytes):
+        """triples: uint32 [n, 3] (the .bkwig payload), segs: TABLE_SEG_DTYPE array, names: the bytes name_off / name_len point
+        into -> the table text (size query, then the text)"""
+        t = np.ascontiguousarray(triples, dtype=np.uint32).reshape(-1, 3)
+        segs = np.ascontiguousarray(segs, dtype=TABLE_SEG_DTYPE)
+        nb = np.frombuffer(names, dtype=np.uint8)
+        args = (fmt, _p(t) if len(t) else None, len(t), _p(segs) if len(segs) else None, len(segs), _p(nb) if len(nb) else None, len(nb))
+        rc, need = self.format_table_raw(*args, None, 0)
+        _check(rc)
+        out = np.zeros(max(need, 1), dtype=np.uint8)
+        rc, need = self.format_table_raw(*args, _p(out), need)
+        _check(rc)
+        return out[:need].tobytes()
 
     def lookup_keys(self, keys):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)

@@ -32,6 +32,7 @@ using namespace kq;
 #include "kq_dbimage.h"
 #include "kq_subgraph.h"
 #include "kq_variants.h"
+#include "kq_table.h"
 
 // ================================================================================================
 // host side
@@ -229,6 +230,8 @@ struct kq_handle {
     DevMem hot;                          // k_count_regions' list of skewed regions
     uint64_t var_batch = 0;              // KQ_OPT_VARIANT_BATCH: searches per batch of kq_search_variants, 0 = from the scratch budget
     uint64_t sg_batch = 0;               // KQ_OPT_SUBGRAPH_BATCH: searches per batch of kq_subgraph_best_first, 0 = from the scratch budget
+    std::vector<DevMem> user_mem;        // kq_dev_alloc: blocks lent to a caller that does not link the runtime
+    DevMem tab_segs;                     // kq_per_base_triples_dev: the segment lists of the last call (it returns before its kernel ends)
 
     TableView view() const {
         TableView v; v.slots = slots.as<Slot>() - (reg_lo() << REGION_SHIFT); v.n_regions = n_regions; v.hc = hc.as<HcSlot>(); v.hc_mask = hc_cap - 1; v.st = d_state(); v.k = (uint32_t)k;
@@ -2075,6 +2078,129 @@ int kq_lookup_sequence(kq_handle* h, const char* bases, uint64_t len, uint32_t c
     }
     if (!rc) for (int i = 0; i < 3; ++i) counters[i] += c[i];
     return rc;
+}
+
+// ---- per-base tables: device memory for the CLI, triples, text ---------------------------------------------------------
+void* kq_dev_alloc(kq_handle* h, uint64_t bytes) {
+    if (!h || hipSetDevice(h->device) != hipSuccess) return nullptr;
+    DevMem m;
+    if (m.alloc(bytes ? (size_t)bytes : 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (hipMemsetAsync(m.get(), 0, m.bytes(), h->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }      // (what kq_lookup_sequence_dev asks of a per-base array)
+    h->user_mem.push_back(std::move(m));
+    return h->user_mem.back().get();
+}
+void kq_dev_free(kq_handle* h, void* p) {
+    if (!h || !p) return;
+    (void)hipSetDevice(h->device);
+    for (size_t i = 0; i < h->user_mem.size(); ++i)
+        if (h->user_mem[i].get() == p) { h->user_mem.erase(h->user_mem.begin() + (ptrdiff_t)i); return; }
+}
+int kq_copy_async(kq_handle* h, void* dst, const void* src, uint64_t bytes, int kind) {
+    if (!h || ((!dst || !src) && bytes)) return fail(KQ_ERR_INVALID, "null argument");
+    if (kind != KQ_COPY_TO_DEVICE && kind != KQ_COPY_TO_HOST) return fail(KQ_ERR_INVALID, "unknown copy kind %d", kind);
+    HIPC(hipSetDevice(h->device));
+    if (bytes) HIPC(hipMemcpyAsync(dst, src, (size_t)bytes, kind == KQ_COPY_TO_DEVICE ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, h->stream));
+    return KQ_OK;
+}
+
+int kq_per_base_triples_dev(kq_handle* h, const kq_dbgbase* d_per_base, const uint64_t* seg_start, const uint64_t* seg_len, uint64_t n_segs, uint32_t* d_triples) {
+    if (!h || ((!seg_start || !seg_len) && n_segs)) return fail(KQ_ERR_INVALID, "null argument");
+    if (n_segs >= 0xFFFFFFFFull) return fail(KQ_ERR_INVALID, "%llu segments: fewer than 2^32 - 1 per call", (unsigned long long)n_segs);
+    std::vector<unsigned long long> lists(2 * (size_t)n_segs + 1);          // seg_start[n_segs], out_start[n_segs + 1]
+    unsigned long long total = 0;
+    for (uint64_t s = 0; s < n_segs; ++s) { lists[s] = seg_start[s]; lists[n_segs + s] = total; total += seg_len[s]; }
+    lists[2 * n_segs] = total;
+    if (!total) return KQ_OK;
+    if (!d_per_base || !d_triples) return fail(KQ_ERR_INVALID, "null argument");
+    HIPC(hipSetDevice(h->device));
+    HIPC(h->tab_segs.ensure(lists.size() * 8));                          // (frees the previous lists only after the device has finished with them)
+    unsigned long long* d_lists = h->tab_segs.as<unsigned long long>();
+    HIPC(hipMemcpyAsync(d_lists, lists.data(), lists.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIPC(hipStreamSynchronize(h->stream));                                // `lists` is pageable and leaves scope
+    hipLaunchKernelGGL(k_tab_triples, dim3(grid_for(h, total, 256)), dim3(256), 0, h->stream, d_per_base, (const unsigned long long*)d_lists,
+                       (const unsigned long long*)(d_lists + n_segs), (uint32_t)n_segs, (uint64_t)total, d_triples);
+    HIPC(hipGetLastError());
+    return KQ_OK;
+}
+
+// the checks of kq_format_table*, and the lines before every piece
+static int tab_check(kq_handle* h, int format, const void* triples, uint64_t n_triples, const kq_table_seg* segs, uint64_t n_segs, const char* names, uint64_t names_len,
+                     uint64_t* n_out, std::vector<unsigned long long>* line_start) {
+    if (!h || !n_out || (!segs && n_segs) || (!triples && n_triples) || (!names && names_len)) return fail(KQ_ERR_INVALID, "null argument");
+    if (format != KQ_TABLE_KWIG && format != KQ_TABLE_BED && format != KQ_TABLE_CSV) return fail(KQ_ERR_INVALID, "unknown table format %d", format);
+    if (n_segs >= 0xFFFFFFFFull) return fail(KQ_ERR_INVALID, "%llu pieces: format fewer than 2^32 lines per call", (unsigned long long)n_segs);
+    line_start->assign((size_t)n_segs + 1, 0);
+    unsigned long long lines = 0;
+    for (uint64_t p = 0; p < n_segs; ++p) {
+        const kq_table_seg& s = segs[p];
+        if (s.n_ctx > (uint32_t)(h->k - 1) || s.n_ctx > s.first) return fail(KQ_ERR_INVALID, "piece %llu: n_ctx %u exceeds k - 1 = %d or its first triple %llu", (unsigned long long)p, s.n_ctx, h->k - 1, (unsigned long long)s.first);
+        if (s.first > n_triples || s.n > n_triples - s.first) return fail(KQ_ERR_INVALID, "piece %llu runs past the %llu triples", (unsigned long long)p, (unsigned long long)n_triples);
+        if (s.name_len > TAB_MAX_NAME || s.name_off > names_len || s.name_len > names_len - s.name_off) return fail(KQ_ERR_INVALID, "piece %llu: its name lies outside the names (or is longer than %u bytes)", (unsigned long long)p, TAB_MAX_NAME);
+        (*line_start)[p] = lines;
+        lines += s.n + ((format == KQ_TABLE_KWIG && (s.flags & KQ_TABLE_SEG_HEADER)) ? 1 : 0);
+        if (lines >= (1ull << 32)) return fail(KQ_ERR_INVALID, "2^32 lines or more in one call: format in smaller calls");
+    }
+    (*line_start)[n_segs] = lines;
+    return KQ_OK;
+}
+// d_triples on the device; `out` on the device (out_on_host false) or on the host
+static int tab_format(kq_handle* h, int format, const uint32_t* d_triples, const kq_table_seg* segs, uint64_t n_segs, const char* names, uint64_t names_len,
+                      const std::vector<unsigned long long>& line_start, char* out, bool out_on_host, uint64_t cap, uint64_t* n_out) {
+    *n_out = 0;
+    const uint64_t n_lines = line_start[n_segs];
+    if (!n_lines) return KQ_OK;
+    hipStream_t st = h->stream;
+    const uint64_t n_tiles = (n_lines + TAB_TILE - 1) / TAB_TILE, n_chunks = (n_tiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    DevScope mem;
+    kq_table_seg* d_segs = nullptr;
+    unsigned long long *d_ls = nullptr, *d_tile = nullptr, *d_sums = nullptr;
+    char* d_names = nullptr;
+    if (mem.alloc((void**)&d_segs, n_segs * sizeof(kq_table_seg)) != hipSuccess || mem.alloc((void**)&d_ls, (n_segs + 1) * 8) != hipSuccess ||
+        mem.alloc((void**)&d_names, names_len) != hipSuccess || mem.alloc((void**)&d_tile, n_tiles * 8) != hipSuccess || mem.alloc((void**)&d_sums, (n_chunks + 2) * 8) != hipSuccess)
+        return fail(KQ_ERR_NOMEM, "no device memory for the placement of %llu lines", (unsigned long long)n_lines);
+    unsigned long long* d_total = d_sums + n_chunks + 1;
+    HIPC(hipMemcpyAsync(d_segs, segs, n_segs * sizeof(kq_table_seg), hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(d_ls, line_start.data(), (n_segs + 1) * 8, hipMemcpyHostToDevice, st));
+    if (names_len) HIPC(hipMemcpyAsync(d_names, names, names_len, hipMemcpyHostToDevice, st));
+    const TabArgs a{d_triples, d_segs, d_ls, d_names, n_lines, (uint32_t)n_segs, format, h->k};
+    const dim3 grid(grid_for(h, n_tiles, 1, 8));
+    // 1. line lengths -> bytes per tile, 2. tile offsets and the size
+    hipLaunchKernelGGL(k_tab_len, grid, dim3(TAB_THREADS), 0, st, a, d_tile);
+    scan_u64(h, d_tile, n_tiles, d_sums, d_total);
+    HIPC(hipGetLastError());
+    unsigned long long total = 0;
+    HIPC(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    *n_out = total;
+    if (!out) return KQ_OK;
+    if (total > cap) return fail(KQ_ERR_CAPACITY, "the table text takes %llu bytes: the buffer holds %llu", total, (unsigned long long)cap);
+    // 3. the text
+    char* d_out = out;
+    if (out_on_host && mem.alloc((void**)&d_out, total) != hipSuccess) return fail(KQ_ERR_NOMEM, "no device memory for %llu bytes of table text", total);
+    hipLaunchKernelGGL(k_tab_write, grid, dim3(TAB_THREADS), 0, st, a, (const unsigned long long*)d_tile, (uint64_t)total, d_out);
+    HIPC(hipGetLastError());
+    if (out_on_host) HIPC(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return KQ_OK;
+}
+int kq_format_table_dev(kq_handle* h, int format, const uint32_t* d_triples, uint64_t n_triples, const kq_table_seg* segs, uint64_t n_segs, const char* names,
+                        uint64_t names_len, char* d_out, uint64_t cap, uint64_t* n_out) {
+    std::vector<unsigned long long> line_start;
+    int rc = tab_check(h, format, d_triples, n_triples, segs, n_segs, names, names_len, n_out, &line_start);
+    if (rc) return rc;
+    HIPC(hipSetDevice(h->device));
+    return tab_format(h, format, d_triples, segs, n_segs, names, names_len, line_start, d_out, false, cap, n_out);
+}
+int kq_format_table(kq_handle* h, int format, const uint32_t* triples, uint64_t n_triples, const kq_table_seg* segs, uint64_t n_segs, const char* names,
+                    uint64_t names_len, char* out, uint64_t cap, uint64_t* n_out) {
+    std::vector<unsigned long long> line_start;
+    int rc = tab_check(h, format, triples, n_triples, segs, n_segs, names, names_len, n_out, &line_start);
+    if (rc) return rc;
+    HIPC(hipSetDevice(h->device));
+    void* d = nullptr;
+    rc = stage_in(h, triples, (size_t)n_triples * 12, &d);
+    if (rc) return rc;
+    return tab_format(h, format, (const uint32_t*)d, segs, n_segs, names, names_len, line_start, out, true, cap, n_out);
 }
 
 // ---- candidate-error search support ---------------------------------------------------------------

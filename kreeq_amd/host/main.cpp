@@ -3,6 +3,7 @@
 // (src/main.cpp:78-97, :220-229; src/input.cpp:76-152; src/kreeq-output.cpp:34-136;
 // src/graph-builder.cpp:288-293; src/kreeq.cpp:78-106).  All compute goes through the C ABI
 // (include/kreeq_amd.h) to the GPU; this file is plumbing: argument parsing, file formats, text.
+#include <fcntl.h>
 #include <getopt.h>
 #include <sys/resource.h>
 #include <sys/stat.h>
@@ -11,14 +12,17 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cerrno>
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <future>
 #include <iostream>
 #include <map>
+#include <sstream>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -69,6 +73,15 @@ void kq_or_die(int rc) { if (rc != KQ_OK) die(std::string("Error: ") + kq_last_e
 bool db_device() { static const bool on = [] { const char* e = getenv("KQ_DB_DEVICE"); return e && atoi(e) != 0; }(); return on; }
 // KQ_SUBGRAPH_DEVICE=1: `kreeq subgraph --traversal-algorithm best-first` searches on the GPU (kq_subgraph_best_first); off by default
 bool subgraph_device() { static const bool on = [] { const char* e = getenv("KQ_SUBGRAPH_DEVICE"); return e && atoi(e) != 0; }(); return on; }
+// KQ_TABLE_DEVICE=1: the per-base outputs of validate (-o x.kwig / .bkwig / .bed / .csvtable) are made on the GPU: the lookup
+// keeps its per-base array there, kq_per_base_triples_dev orients it and kq_format_table_dev writes the text; off by default,
+// and every file and stdout are byte-identical in both modes.  KQ_TABLE_CHUNK_LINES: lines (positions) per formatted chunk.
+// KQ_TABLE_TRACE=1 prints the wall clock of the steps to stderr.
+bool table_device() { static const bool on = [] { const char* e = getenv("KQ_TABLE_DEVICE"); return e && atoi(e) != 0; }(); return on; }
+uint64_t table_chunk_lines() { const char* e = getenv("KQ_TABLE_CHUNK_LINES"); return e ? (uint64_t)std::max(1ll, atoll(e)) : ((uint64_t)1 << 20); }
+constexpr uint64_t kTableDeviceCallBytes = 1ull << 30;          // joined text per lookup call of the device writers (as kVcfDeviceCallBytes)
+const char* kTableDeviceLine = "per-base table written by the device formatter";
+const char* kTableHostLine = "per-base table written by the host writer";
 struct DbTrace {
     const char* what; double t0 = now_s(); uint64_t pcie = 0;
     explicit DbTrace(const char* w) : what(w) {}
@@ -252,14 +265,17 @@ struct Engine {
             }
         }
     }
-    void write_bkwig(const std::string& path) {
-        std::ofstream ofs(path, std::ios::trunc | std::ios::out | std::ios::binary);
+    typedef std::vector<std::vector<std::pair<uint64_t, uint64_t>>> SegmentLists;      // per sequence: (start, length) of its segments
+    SegmentLists all_segments() const {
+        SegmentLists segs;
+        for (auto& s : genome.seqs) segs.push_back(segments_of(s.seq));
+        return segs;
+    }
+    void write_bkwig_index(std::ostream& ofs, const SegmentLists& segs) const {
         uint8_t k8 = (uint8_t)k;
         ofs.write((const char*)&k8, 1);
         uint32_t nPaths = (uint32_t)genome.seqs.size();
         ofs.write((const char*)&nPaths, 4);
-        std::vector<std::vector<std::pair<uint64_t, uint64_t>>> segs;
-        for (auto& s : genome.seqs) segs.push_back(segments_of(s.seq));
         for (size_t s = 0; s < genome.seqs.size(); ++s) {                            // writeIndex :305-355
             uint16_t hl = (uint16_t)genome.seqs[s].header.size();
             ofs.write((const char*)&hl, 2);
@@ -273,6 +289,11 @@ struct Engine {
                 ofs.write((const char*)&step, 1);
             }
         }
+    }
+    void write_bkwig(const std::string& path) {
+        std::ofstream ofs(path, std::ios::trunc | std::ios::out | std::ios::binary);
+        const SegmentLists segs = all_segments();
+        write_bkwig_index(ofs, segs);
         for (size_t s = 0; s < genome.seqs.size(); ++s)
             for (auto& seg : segs[s]) {
                 const kq_dbgbase* b = per_base.data() + genome.offset[s] + seg.first;
@@ -309,6 +330,171 @@ struct Engine {
             }
         }
     }
+    // ---- KQ_TABLE_DEVICE=1: the same four files from the device ---------------------------------------------------------
+    // Whole sequences are grouped into calls of at most kTableDeviceCallBytes of joined text.  Per call the lookup fills a
+    // per-base array that stays on the device, kq_per_base_triples_dev makes the .bkwig payload of the call's segments from it,
+    // and that payload is either copied out as it is (.bkwig) or formatted in chunks of at most KQ_TABLE_CHUNK_LINES positions
+    // (kq_format_table_dev).  Two page-locked buffers take turns: the copy and the format of chunk j + 1 run while a writer
+    // thread hands chunk j to the file with one write() call.
+    bool table_device_fits() const {
+        for (auto& s : genome.seqs) if (s.seq.size() + 1 > kTableDeviceCallBytes) return false;
+        return true;
+    }
+    struct TableOut {                                                    // the file, the two buffers and the write in flight
+        int fd = -1;
+        char* buf[2] = {nullptr, nullptr};
+        uint64_t cap[2] = {0, 0};
+        std::future<double> pending;
+        uint64_t n = 0, bytes = 0;
+        double t_write = 0;
+        ~TableOut() { if (pending.valid()) pending.wait(); for (char* p : buf) kq_host_free(p); if (fd >= 0) ::close(fd); }
+        static double write_all(int fd, const char* p, uint64_t len) {
+            const double t0 = now_s();
+            while (len) {                                                // one call, unless the kernel takes less
+                const ssize_t w = ::write(fd, p, (size_t)len);
+                if (w < 0) { if (errno == EINTR) continue; die(std::string("Error: write failed: ") + strerror(errno)); }
+                p += w; len -= (uint64_t)w;
+            }
+            return now_s() - t0;
+        }
+        void direct(const void* p, uint64_t len) { wait(); t_write += write_all(fd, (const char*)p, len); bytes += len; }
+        void wait() { if (pending.valid()) t_write += pending.get(); }
+        // the buffer the next chunk goes to, with room for `need` bytes (its previous content has reached the file)
+        char* next(uint64_t need) {
+            const int b = (int)(n & 1);
+            if (cap[b] < need) {
+                kq_host_free(buf[b]);
+                cap[b] = need + need / 8 + 4096;
+                buf[b] = (char*)kq_host_alloc(cap[b]);
+                if (!buf[b]) die("Error: no page-locked memory for " + std::to_string(cap[b]) + " bytes of table output");
+            }
+            return buf[b];
+        }
+        // the chunk in next()'s buffer is complete: wait for the write before it, start this one
+        void submit(uint64_t len) {
+            const int b = (int)(n & 1);
+            wait();
+            const int f = fd; const char* p = buf[b];
+            pending = std::async(std::launch::async, [f, p, len] { return write_all(f, p, len); });
+            bytes += len; ++n;
+        }
+    };
+    void write_per_base_device(const std::string& path, const std::string& ext) {
+        verbose("Validating sequence");
+        const int fmt = ext == "kwig" ? KQ_TABLE_KWIG : ext == "bed" ? KQ_TABLE_BED : ext == "csvtable" ? KQ_TABLE_CSV : 0;      // 0: .bkwig
+        const bool expanded = fmt == KQ_TABLE_BED || fmt == KQ_TABLE_CSV;
+        const SegmentLists segs = all_segments();
+        TableOut out;
+        out.fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        if (out.fd < 0) die("Error: cannot write " + path + ": " + strerror(errno));
+        if (fmt == KQ_TABLE_KWIG) { const std::string head = std::to_string(k) + "\n"; out.direct(head.data(), head.size()); }
+        if (fmt == 0) { std::ostringstream index; write_bkwig_index(index, segs); const std::string s = index.str(); out.direct(s.data(), s.size()); }
+        std::string names;
+        std::vector<uint32_t> name_off;
+        for (auto& s : genome.seqs) { name_off.push_back((uint32_t)names.size()); names += s.header; }
+        const uint64_t chunk = table_chunk_lines();
+        double t_lookup = 0, t_format = 0, t_copy = 0;
+        char* d_text = nullptr;
+        uint64_t d_text_cap = 0;
+        auto dev_alloc = [&](uint64_t bytes) { void* p = kq_dev_alloc(h, bytes); if (!p) die("Error: no device memory for " + std::to_string(bytes) + " bytes of the per-base table"); return p; };
+        for (size_t lo = 0; lo < genome.seqs.size();) {
+            size_t hi = lo;
+            uint64_t len = 0;
+            while (hi < genome.seqs.size() && (hi == lo || len + genome.seqs[hi].seq.size() + 1 <= kTableDeviceCallBytes)) { len += genome.seqs[hi].seq.size() + 1; ++hi; }
+            // 1. lookup with the per-base array on the device, 2. the triples of the call's segments
+            double t0 = now_s();
+            std::vector<uint64_t> seg_start, seg_len;
+            uint64_t n_triples = 0;
+            for (size_t s = lo; s < hi; ++s)
+                for (auto& seg : segs[s]) { seg_start.push_back(genome.offset[s] - genome.offset[lo] + seg.first); seg_len.push_back(seg.second); n_triples += seg.second; }
+            char* d_bases = (char*)dev_alloc(len);
+            kq_dbgbase* d_pb = (kq_dbgbase*)dev_alloc(len * sizeof(kq_dbgbase));                // (zero-filled)
+            uint64_t* d_ctr = (uint64_t*)dev_alloc(3 * sizeof(uint64_t));
+            uint32_t* d_triples = (uint32_t*)dev_alloc(n_triples * 12);
+            kq_or_die(kq_copy_async(h, d_bases, genome.joined.data() + genome.offset[lo], len, KQ_COPY_TO_DEVICE));
+            kq_or_die(kq_lookup_sequence_dev(h, d_bases, len, ui.covCutOff, 0, (uint16_t)map_count, d_pb, d_ctr));
+            kq_or_die(kq_per_base_triples_dev(h, d_pb, seg_start.data(), seg_len.data(), seg_start.size(), d_triples));
+            uint64_t ctr[3] = {0, 0, 0};
+            kq_or_die(kq_copy_async(h, ctr, d_ctr, sizeof ctr, KQ_COPY_TO_HOST));
+            kq_or_die(kq_sync(h));
+            for (int i = 0; i < 3; ++i) counters[i] += ctr[i];
+            kq_dev_free(h, d_bases); kq_dev_free(h, d_pb); kq_dev_free(h, d_ctr);
+            t_lookup += now_s() - t0;
+            if (fmt == 0) {                                              // .bkwig: the payload is the triples
+                for (uint64_t a = 0; a < n_triples; a += chunk) {
+                    const uint64_t bytes = std::min(chunk, n_triples - a) * 12;
+                    char* dst = out.next(bytes);
+                    t0 = now_s();
+                    kq_or_die(kq_copy_async(h, dst, d_triples + a * 3, bytes, KQ_COPY_TO_HOST));
+                    kq_or_die(kq_sync(h));
+                    t_copy += now_s() - t0;
+                    out.submit(bytes);
+                }
+            } else {
+                // 3. the text, in chunks of at most `chunk` positions: whole segments or parts of one (an expanded part has the
+                //    k - 1 positions before it as its history)
+                std::vector<kq_table_seg> pieces;
+                uint64_t lines = 0;
+                auto flush = [&]() {
+                    if (pieces.empty()) return;
+                    uint64_t need = 0;
+                    t0 = now_s();
+                    kq_or_die(kq_format_table_dev(h, fmt, d_triples, n_triples, pieces.data(), pieces.size(), names.data(), names.size(), nullptr, 0, &need));
+                    if (need > d_text_cap) { kq_dev_free(h, d_text); d_text_cap = need + need / 8 + 4096; d_text = (char*)dev_alloc(d_text_cap); }
+                    char* dst = out.next(need);
+                    kq_or_die(kq_format_table_dev(h, fmt, d_triples, n_triples, pieces.data(), pieces.size(), names.data(), names.size(), d_text, d_text_cap, &need));
+                    t_format += now_s() - t0;
+                    t0 = now_s();
+                    kq_or_die(kq_copy_async(h, dst, d_text, need, KQ_COPY_TO_HOST));
+                    kq_or_die(kq_sync(h));
+                    t_copy += now_s() - t0;
+                    out.submit(need);
+                    pieces.clear(); lines = 0;
+                };
+                uint64_t first = 0;                                      // triple index of the segment inside the call
+                for (size_t s = lo; s < hi; ++s)
+                    for (auto& seg : segs[s]) {
+                        for (uint64_t done = 0; done < seg.second;) {
+                            const uint64_t take = std::min(seg.second - done, chunk - lines);
+                            kq_table_seg p{};
+                            p.first = first + done; p.n = take; p.abs_pos = seg.first + done;
+                            p.name_off = name_off[s]; p.name_len = (uint32_t)genome.seqs[s].header.size();
+                            p.n_ctx = expanded ? (uint32_t)std::min<uint64_t>(done, (uint64_t)k - 1) : 0;
+                            p.flags = done == 0 ? KQ_TABLE_SEG_HEADER : 0;
+                            pieces.push_back(p);
+                            lines += take; done += take;
+                            if (lines >= chunk) flush();
+                        }
+                        first += seg.second;
+                    }
+                flush();
+            }
+            kq_dev_free(h, d_triples);                                   // (every chunk of the call has left the device)
+            lo = hi;
+        }
+        out.wait();
+        kq_dev_free(h, d_text);
+        print_qv();
+        static const bool trace = [] { const char* e = getenv("KQ_TABLE_TRACE"); return e && atoi(e) != 0; }();
+        if (trace) fprintf(stderr, "[table] device: lookup %.3f s, format %.3f s, copy %.3f s, write %.3f s, %llu bytes\n", t_lookup, t_format, t_copy, out.t_write, (unsigned long long)out.bytes);
+    }
+    // the four per-base outputs, by whichever side may write them: `ranged` = the per-base vector was filled over map-range
+    // passes on the host (it accumulates across the ranges there)
+    void write_per_base(const std::string& ext, bool ranged) {
+        if (!ranged && table_device() && !ui.inSequence.empty() && table_device_fits()) {
+            verbose(kTableDeviceLine);
+            write_per_base_device(ui.outFile, ext);
+            return;
+        }
+        if (!ranged) validate_sequences(true);
+        verbose(kTableHostLine);
+        const double t0 = now_s();
+        if (ext == "kwig") write_kwig(ui.outFile);
+        else if (ext == "bkwig") write_bkwig(ui.outFile);
+        else write_table(ui.outFile, ext);
+        static const bool trace = [] { const char* e = getenv("KQ_TABLE_TRACE"); return e && atoi(e) != 0; }();
+        if (trace) fprintf(stderr, "[table] host: write %.3f s\n", now_s() - t0);
+    }
     // -o vcf / -o x.vcf: DBG::correctSequences (src/variants.cpp:40-50) + gfalibs' VCF writer; "-o vcf" names no file:
     // the records go to stdout (validateFiles/test.50.tst)
     void write_vcf() { write_vcf(graph_of_handle(h)); }
@@ -341,7 +527,8 @@ struct Engine {
         if (ext == "vcf") { if (ui.mode == 0) write_vcf(); return; }   // case 6: correctSequences, then printVCF (src/kreeq-output.cpp:74-82, :124-127)
         // the reference's first switch has no case for .kreeq / .hist, so they fall to `default:` like every other
         // extension and validate too (src/kreeq-output.cpp:62-72); validateSequences returns at once without -f
-        if (ui.mode == 0) validate_sequences(per_base_out);
+        if (per_base_out && ui.mode == 0) { write_per_base(ext, false); return; }      // validates, on the device or through validate_sequences
+        if (ui.mode == 0) validate_sequences(false);
         if (ext == "kreeq") { write_kreeq_db(ui.outFile); verbose("Database written"); }
         else if (ext == "kwig") write_kwig(ui.outFile);
         else if (ext == "bkwig") write_bkwig(ui.outFile);
@@ -742,9 +929,7 @@ int run_passes(Engine& e, const DbSource* db) {
     }
     if (want_validate) {
         e.print_qv();
-        if (ext == "kwig") e.write_kwig(ui.outFile);
-        else if (ext == "bkwig") e.write_bkwig(ui.outFile);
-        else if (ext == "bed" || ext == "csvtable") e.write_table(ui.outFile, ext);
+        if (per_base_out) e.write_per_base(ext, true);                   // the per-base vector accumulated across the ranges: the host writers
     }
     if (ext == "hist") {
         std::ofstream ofs(ui.outFile);
