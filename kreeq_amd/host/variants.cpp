@@ -13,11 +13,11 @@
 // layout here is inferred from its one golden file (validateFiles/test.50.tst) and documented at vcf_record().
 #include "variants.h"
 
+#include "cli_common.h"
+#include "cli_plan.h"
 #include "graph_search.h"
 
 #include <algorithm>
-#include <chrono>
-#include <cstdlib>
 #include <deque>
 #include <stdexcept>
 #include <thread>
@@ -153,15 +153,10 @@ GraphSource graph_of_handle(kq_handle* h) {
 
 namespace {
 
-// KQ_VCF_DEVICE=1: the candidate-error searches run on the GPU, one per lane (kq_search_variants); off by default
-bool vcf_device() { static const bool on = [] { const char* e = getenv("KQ_VCF_DEVICE"); return e && atoi(e) != 0; }(); return on; }
-
 // The searches of seqs[lo, hi) in one kq_search_variants call over their joined text -> sites appended to `out`
 void device_call(kq_handle* h, const std::vector<SeqRecord>& seqs, size_t lo, size_t hi, int kmer_depth, int max_span, uint32_t cov_cutoff,
                  std::vector<kq_variant_path>& paths, std::vector<char>& bases, std::vector<VariantSite>& out, uint64_t& n_calls) {
-    std::string joined;
-    std::vector<uint64_t> offset;
-    for (size_t si = lo; si < hi; ++si) { offset.push_back(joined.size()); joined += seqs[si].seq; joined.push_back('\n'); }
+    const auto [joined, offset] = join_sequences(seqs, lo, hi);
     uint64_t n_paths = 0, n_seq = 0;
     int rc = kq_search_variants(h, joined.data(), joined.size(), kmer_depth, max_span, cov_cutoff, paths.data(), paths.size(), &n_paths, bases.data(), bases.size(), &n_seq);
     ++n_calls;
@@ -192,22 +187,18 @@ void device_call(kq_handle* h, const std::vector<SeqRecord>& seqs, size_t lo, si
 std::vector<VariantSite> find_candidate_errors_device(kq_handle* h, const std::vector<SeqRecord>& seqs, int kmer_depth, int max_span, uint32_t cov_cutoff,
                                                       const std::function<void(const std::string&)>& log) {
     static_assert((int)VAR_SNV == KQ_VAR_SNV && (int)VAR_INS == KQ_VAR_INS && (int)VAR_DEL == KQ_VAR_DEL && (int)VAR_COM == KQ_VAR_COM, "path types");
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
+    const double t0 = now_s();
     std::vector<VariantSite> out;
     std::vector<kq_variant_path> paths(1 << 16);                         // modest caps; a call that needs more says how much
     std::vector<char> bases(1 << 22);
     uint64_t n_calls = 0, n_records = 0;
-    for (size_t lo = 0; lo < seqs.size();) {                             // whole sequences, at most kVcfDeviceCallBytes of joined text per call
-        size_t hi = lo;
-        uint64_t bytes = 0;
-        while (hi < seqs.size() && (hi == lo || bytes + seqs[hi].seq.size() + 1 <= kVcfDeviceCallBytes)) { bytes += seqs[hi].seq.size() + 1; ++hi; }
+    for (size_t lo = 0, hi; lo < seqs.size(); lo = hi) {                 // whole sequences, at most kDeviceCallBytes of joined text per call
+        hi = next_call(seqs, lo, kDeviceCallBytes);
         device_call(h, seqs, lo, hi, kmer_depth, max_span, cov_cutoff, paths, bases, out, n_calls);
-        lo = hi;
     }
     for (auto& v : out) n_records += v.paths.size();
     if (log) log("Device searches: " + std::to_string(n_calls) + " calls, " + std::to_string(out.size()) + " sites, " + std::to_string(n_records) + " paths; " +
-                 std::to_string(now() - t0) + " s");
+                 std::to_string(now_s() - t0) + " s");
     return out;
 }
 
@@ -215,9 +206,9 @@ std::vector<VariantSite> find_candidate_errors_device(kq_handle* h, const std::v
 
 std::vector<VariantSite> find_candidate_errors(const GraphSource& g, int k, const std::vector<SeqRecord>& seqs, int kmer_depth, int max_span,
                                                uint32_t cov_cutoff, const std::function<void(const std::string&)>& log) {
-    if (vcf_device()) {
-        bool fits = g.resident && kmer_depth >= 0 && kmer_depth <= kVcfDeviceMaxDepth && max_span >= kVcfDeviceMinSpan && max_span <= kVcfDeviceMaxSpan;
-        for (auto& r : seqs) fits = fits && r.seq.size() + 1 <= kVcfDeviceCallBytes;
+    if (env_flag("KQ_VCF_DEVICE")) {                                     // the searches run on the GPU, one per lane (kq_search_variants); off by default
+        const bool fits = g.resident && kmer_depth >= 0 && kmer_depth <= kVcfDeviceMaxDepth && max_span >= kVcfDeviceMinSpan && max_span <= kVcfDeviceMaxSpan &&
+                          all_fit(seqs, kDeviceCallBytes);
         if (fits) {
             if (log) log("candidate-error search ran as the device search");
             return find_candidate_errors_device(g.resident, seqs, kmer_depth, max_span, cov_cutoff, log);
@@ -225,9 +216,7 @@ std::vector<VariantSite> find_candidate_errors(const GraphSource& g, int k, cons
     }
     if (log) log("candidate-error search ran as the host search");
     // 1. device pre-filter over the whole assembly (sequences joined by a non-base byte)
-    std::string joined;
-    std::vector<uint64_t> offset;
-    for (auto& r : seqs) { offset.push_back(joined.size()); joined += r.seq; joined.push_back('\n'); }
+    const auto [joined, offset] = join_sequences(seqs, 0, seqs.size());
     std::vector<uint8_t> flags(joined.size());
     g.branch_scan(joined, cov_cutoff, flags);
 
@@ -237,11 +226,8 @@ std::vector<VariantSite> find_candidate_errors(const GraphSource& g, int k, cons
     uint64_t n_pos = 0;
     for (size_t si = 0; si < seqs.size(); ++si) {
         const std::string& seq = seqs[si].seq;
-        for (uint64_t i = 0; i < seq.size();) {                          // segments = runs of bases (gfalibs splits at N)
-            if (ctoi(seq[i]) > 3) { ++i; continue; }
-            uint64_t j = i;
-            while (j < seq.size() && ctoi(seq[j]) <= 3) ++j;
-            const uint64_t len = j - i;
+        for (auto& seg : segments_of(seq)) {
+            const uint64_t i = seg.first, len = seg.second;
             if (len >= (uint64_t)k) {
                 const uint64_t kcount = len - k + 1;
                 std::vector<uint8_t> str(len);
@@ -278,11 +264,9 @@ std::vector<VariantSite> find_candidate_errors(const GraphSource& g, int k, cons
                     searches.push_back(std::move(s));
                 }
             }
-            i = j;
         }
     }
     if (log) log("Candidate positions after the device pre-filter: " + std::to_string(searches.size()) + " of " + std::to_string(n_pos));
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_adv = 0, t_sort = 0, t_look = 0, t_cache = 0;
     size_t n_rounds = 0, n_keys = 0;
 
@@ -299,7 +283,7 @@ std::vector<VariantSite> find_candidate_errors(const GraphSource& g, int k, cons
             // the searches of a round are independent (each reads the cache and its own state): a few host threads share
             // them when there are enough (HiFi-scale inputs flag tens of thousands of positions per batch)
             const size_t n_live = hi - lo;
-            double t0 = now();
+            double t0 = now_s();
             unsigned n_thr = std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
             if (n_live < 512) n_thr = 1;
             if (n_thr > 1) {
@@ -316,22 +300,22 @@ std::vector<VariantSite> find_candidate_errors(const GraphSource& g, int k, cons
                 for (size_t i = lo; i < hi; ++i) if (!searches[i].done) advance(searches[i], cache, k, kmer_depth, cov_cutoff, want);
             }
             for (size_t i = lo; i < hi && !any; ++i) any = !searches[i].done;
-            t_adv += now() - t0; t0 = now();
+            t_adv += now_s() - t0; t0 = now_s();
             if (!any) break;
             std::sort(want.begin(), want.end());
             want.erase(std::unique(want.begin(), want.end()), want.end());
             if (want.empty()) throw std::runtime_error("candidate-error search stalled");
-            t_sort += now() - t0; t0 = now();
+            t_sort += now_s() - t0; t0 = now_s();
             got.resize(want.size());
             g.lookup(want, got);
-            t_look += now() - t0; t0 = now();
+            t_look += now_s() - t0; t0 = now_s();
             cache.reserve(cache.size() + got.size());
             for (auto& e : got) {
                 Node& n = cache[e.key];
                 for (int w = 0; w < 4; ++w) { n.fw[w] = e.fw[w]; n.bw[w] = e.bw[w]; }
                 n.present = e.cov != 0;
             }
-            t_cache += now() - t0;
+            t_cache += now_s() - t0;
             ++n_rounds; n_keys += want.size();
         }
         if (cache.size() > (1u << 24)) cache.clear();                    // bounded memory on large assemblies

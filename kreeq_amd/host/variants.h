@@ -34,10 +34,9 @@ GraphSource graph_of_handle(kq_handle* h);
 // The device limits of kq_search_variants as the CLI uses them.  max_span 0 stays with the host search: the reference pops an
 // empty queue there, and the host search (no target) and the device search (the pop skipped: one target, k-mer c + k) differ.
 constexpr int kVcfDeviceMaxDepth = 253, kVcfDeviceMinSpan = 1, kVcfDeviceMaxSpan = 255;
-constexpr uint64_t kVcfDeviceCallBytes = 1ull << 30;            // joined text per kq_search_variants call
 
 // DBG::correctSequences over all sequences: device pre-filter + host searches with batched device lookups.  With KQ_VCF_DEVICE=1
-// (off by default), a resident table, depth and span inside the device limits and no sequence above kVcfDeviceCallBytes, the
+// (off by default), a resident table, depth and span inside the device limits and no sequence above kDeviceCallBytes (cli_plan.h), the
 // searches run on the device instead (kq_search_variants), whole sequences grouped into calls; the sites are the same.
 std::vector<VariantSite> find_candidate_errors(const GraphSource& g, int k, const std::vector<SeqRecord>& seqs, int kmer_depth, int max_span,
                                                uint32_t cov_cutoff, const std::function<void(const std::string&)>& log = nullptr);
