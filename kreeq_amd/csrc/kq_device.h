@@ -21,20 +21,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kq_formats.h"      // REGION_SHIFT / REGION_SLOTS, HI_K, TILE_STARTS, n_tiles_of, EmitRange
+
 namespace kq {
 
 constexpr uint64_t EMPTY_KEY = ~0ull;          // empty marker of the high-copy table and of LDS region images (never a canonical key / a 56-bit remainder)
 constexpr uint32_t LARGEST = 4294967295u;      // include/kreeq.h:68
 constexpr uint32_t LOW_TIER_MAX = 254;         // src/graph-builder.cpp:166: the 255th instance overflows
-#ifndef KQ_REGION_SHIFT
-#define KQ_REGION_SHIFT 11
-#endif
-constexpr int REGION_SHIFT = KQ_REGION_SHIFT;
-constexpr uint32_t REGION_SLOTS = 1u << REGION_SHIFT;   // 2048 slots x 16 B = 32 KiB in HBM
 constexpr int COV_SHIFT = 56;
 constexpr uint64_t REM_MASK = (1ull << COV_SHIFT) - 1;
 constexpr uint64_t COV8_TOMB = 255;            // cov8 value of a k-mer whose count continues in the high-copy tier
-constexpr int HI_K = 29;                       // k >= HI_K: the hash has more than 56 bits, the region implies its top 8
 
 struct Slot { uint64_t w0, e8; };
 struct HcSlot { uint64_t key; uint64_t cov_hi; uint64_t cnt[8]; };
@@ -329,7 +325,6 @@ __device__ __forceinline__ ulonglong2 img_store(const TableView& t, const uint64
 // registers.  f(pos, fw, prev, next) is called for every start whose k bases are all ACGT;
 // prev/next are the neighbouring base codes or 4 when outside the run.
 constexpr int TILE_THREADS = 256;
-constexpr int TILE_STARTS = 4032;          // 252 lanes x 16 starts; window = 4032 + 16 + 48 bytes
 
 __device__ __forceinline__ void convert16(const uint4& v, bool all_in, int64_t g, int64_t lo_valid, int64_t hi_valid,
                                           uint32_t& codes, uint32_t& inv) {
@@ -471,9 +466,6 @@ __device__ __forceinline__ void tile_lane_scan(const uint32_t* s_codes, const ui
     lane_scan_core<false>(s_codes, s_inv, lo_valid, tile, k,
                           [&](int, bool, uint64_t pos, uint64_t fw, uint64_t rv, uint32_t prev, uint32_t next) { f(pos, fw, rv, prev, next); });
 }
-// k-mer starts a launch may process, in caller positions: lets the host cut a huge batch into
-// slices that share the input array (a slice's scan window includes the neighbouring bases)
-struct EmitRange { uint64_t lo, hi; };
 
 // f(i, valid, fw, rv, prev, next) for all 16 starts; starts outside `er` are reported invalid
 template <class F>
@@ -495,8 +487,6 @@ __device__ __forceinline__ uint32_t tile_lane_count(const uint32_t* s_inv, int k
     for (int i = 0; i < 16; ++i) n += (((ms >> i) & wmask) == 0);
     return n;
 }
-
-inline __host__ __device__ uint64_t n_tiles_of(uint64_t lead, uint64_t len) { return (lead + len + TILE_STARTS - 1) / TILE_STARTS; }
 
 template <class F>
 __device__ __forceinline__ void scan_tiles(const uint8_t* __restrict__ ab, uint64_t lead, uint64_t len, int k, F&& f, const uint16_t* __restrict__ pinv = nullptr) {

@@ -125,9 +125,6 @@ __global__ __launch_bounds__(TILE_THREADS) void k_emit_write(const uint8_t* __re
 // counting pass (count matrix -> exclusive scan), because reservation atomics on a few hundred
 // shared cursors serialise per address (~11 ns each) and were the limiter of the first version.
 
-constexpr int P1_F = 1;                 // hist workgroups per scatter workgroup (the scatter grid is already 6 x the resident workgroups)
-constexpr uint32_t P2_UNIT = 4 * MS_TILE;   // records per work unit of a split level (never crosses a segment); 4 rounds: k_lv_scatter 357 us vs 384 us at 8, 401 us at 16, 430 us at 1
-
 // column of hist workgroup vb in the count matrix: the P1_F hist workgroups whose tiles one scatter
 // workgroup b owns (vb = b, b+G1, ...) are adjacent, so b's output range per bin is contiguous
 __device__ __forceinline__ uint32_t p1_col(uint32_t vb, uint32_t g1) { return (vb % g1) * P1_F + vb / g1; }
@@ -940,7 +937,6 @@ __global__ __launch_bounds__(LV_THREADS, KQ_LVS_OCC_TIGHT) void k_lv_segment_s(c
 __global__ void k_set2(unsigned long long* p, unsigned long long a, unsigned long long b) { p[0] = a; p[1] = b; }
 
 // multi-block exclusive scan helpers (chunks of SCAN_CHUNK elements per workgroup)
-constexpr uint32_t SCAN_CHUNK = 16384;
 __global__ __launch_bounds__(1024) void k_scan_sums(const unsigned long long* __restrict__ a, uint64_t n, unsigned long long* __restrict__ sums) {
     const uint64_t lo = (uint64_t)blockIdx.x * SCAN_CHUNK, hi = lo + SCAN_CHUNK < n ? lo + SCAN_CHUNK : n;
     unsigned long long v = 0;

@@ -16,63 +16,12 @@
 // same 6-bit index pair (AUX_IDX6) or the reference edge byte of include/kreeq.h:6-18 (AUX_EDGE_BYTE).
 #pragma once
 #include "kq_device.h"
-#include "kq_formats.h"      // FMT_*, NB_MAX, PART_MAX_K, NARROW_*
+#include "kq_formats.h"      // FMT_*, NB_MAX, PART_MAX_K, NARROW_*, MS_*, SEG_MAX, AUX_*, PartCfg, P3Set, LevelCfg
 
 namespace kq {
 
-constexpr int MS_THREADS = 256;
-constexpr int MS_ITEMS = 16;
-constexpr int MS_TILE = MS_THREADS * MS_ITEMS;   // 4096 records per multisplit round
-constexpr int SEG_MAX = 65536;                   // segments of one split level (256 hash-prefix buckets x up to 256 sub-buckets)
-constexpr uint32_t SUB_BITS_MAX = 8;
 constexpr int REC_EDGE_SHIFT = 56;
-constexpr int AUX_IDX6 = 0, AUX_EDGE_BYTE = 1, AUX_TIGHT = 2;    // AUX_TIGHT: FMT_TIGHT sets (no lockstep array at all)
 
-struct PartCfg {
-    uint64_t n_regions;   // R
-    uint32_t g_shift;     // coarse bucket = region >> g_shift
-    uint32_t n_coarse;    // bins of P1: ceil(R / 2^g_shift) < NB_MAX (mode 0) or n_parts (mode 1)
-    uint32_t mode;        // 0: bin = coarse bucket of the key's table region; 1: bin = owner part (multi-GPU staging)
-    uint32_t map_count;   // mode 1: gfalibs mapCount
-    uint32_t map_mask;    // map_count - 1 when it is a power of two, else 0
-    uint32_t filt_lo, filt_hi;   // count only k-mers whose map index key % map_count lies in [filt_lo, filt_hi)
-    uint32_t raw_out;     // 1: WIDE records carry the raw key (kq_emit_partitioned_dev), else its table hash
-    uint32_t narrow;      // 1: bin = top NARROW_CBITS hash bits (n_regions is a multiple of 2^NARROW_CBITS), FMT_NARROW records
-    uint32_t owner_sub;   // mode 1: each owner part is cut into 2^owner_sub sub-bins by lane id (a multisplit with a handful of
-                          // bins serialises its LDS rank atomics on a few addresses); the parts stay contiguous.  The histogram
-                          // and the scatter pass give a k-mer the same lane, hence the same sub-bin
-    uint32_t sub_bits;    // narrow: > 0 = a middle level cuts each bucket into 2^sub_bits sub-buckets first (very large tables)
-    uint32_t win_lo, win_hi;   // bin mode 6 (FMT_NARROW and FMT_TOP8 alike): the table is a window of the hash-prefix buckets [win_lo, win_hi): k-mers of other buckets are dropped in P1
-    uint32_t n_rng;       // k_p1_hist bin mode 5 (KQ_OPT_COUNT_MAP_PASSES): count for all n_rng equal map ranges at once, bin = range * 256 + bucket
-};
-
-// One record set of k_count_regions: records sorted by table region (format FMT_*; `aux` = lockstep u8 array or null)
-// and base[0..n_regions] = first record of every region.
-constexpr int P3_MAX_SETS = 64;
-struct P3Set { const uint64_t* recs; const uint8_t* aux; const unsigned long long* base; uint64_t n_max; };
-
-// One level of the record split.  Input records are grouped in n_seg segments (seg_off[0..n_seg]);
-// a record of segment b with table region r goes to bin (r >> out_shift) - (b << (seg_shift - out_shift)).
-//   flat -> coarse buckets : n_seg = 1, seg_shift = 32 (b == 0), out_shift = g_shift, nb = n_coarse
-//   coarse -> regions      : n_seg = n_coarse, seg_shift = g_shift, out_shift = 0, nb = 2^g_shift
-// Output group index = b * nb + bin (== the region id at the last level).
-struct LevelCfg {
-    uint64_t n_regions;
-    uint32_t n_seg, nb, seg_shift, out_shift;
-    uint32_t in_raw;        // 1: the input records hold raw keys (kq_insert_records): this level mixes them
-    uint32_t k;             // k-mer length (width of the table's mix), needed when in_raw
-    uint32_t narrow;        // 1: FMT_NARROW records, segment b = hash-prefix bucket b owning regions [b * nb, (b + 1) * nb)
-    uint32_t top8;          // 1: one segment of packed records, bin = top NARROW_CBITS hash bits; the scatter writes narrow records
-    // narrow levels: segment b = (bucket b >> nr_shift, sub-bucket b & (2^nr_shift - 1)) starts at region
-    // bucket * nr_rps + sub * nr_sub; bin = (region - that) / nr_div (nr_inv = ceil(2^32 / nr_div))
-    uint32_t nr_shift, nr_rps, nr_sub, nr_div, nr_inv;
-    uint32_t nr_mid, nr_fshift, nr_fmask, nr_f24;   // narrow_bin: middle level, 24 - sub_bits, the bits of the position inside a sub-bucket, product fits 32 bits
-    // multi-GPU exchange of narrow records (receive side): spb > 1 = the input has spb segments per logical segment (one
-    // run per peer rank): input segment s belongs to logical segment s / spb, whose units and output groups they share
-    uint32_t spb;
-    uint32_t rep_shift;     // rank replication of the multisplit (block_multisplit's rs), set by the host from nb
-    const uint32_t* rstart = nullptr; // non-null: this (last, narrow) level writes FMT_TIGHT records relative to rstart[region]
-};
 __device__ __forceinline__ uint32_t level_bin(const LevelCfg& lv, uint32_t b, uint64_t region) {
     return (uint32_t)(region >> lv.out_shift) - (lv.seg_shift >= 32 ? 0u : (b << (lv.seg_shift - lv.out_shift)));
 }
@@ -115,7 +64,6 @@ __device__ __forceinline__ uint64_t rec_pack_hash(uint64_t h, bool is_fw, uint32
     return (h >> 8) | ((uint64_t)edge_idx6(is_fw, prev, next) << REC_EDGE_SHIFT);
 }
 
-constexpr uint64_t TIGHT_MIN_REGIONS = 1ull << 16;
 __device__ __forceinline__ uint32_t tight_rec(uint32_t bucket, uint32_t main32, uint32_t aux, uint32_t rstart_r) {
     const uint32_t d = ((bucket << (32 - NARROW_CBITS)) | (main32 >> NARROW_CBITS)) - rstart_r;
     return (d << 16) | ((main32 & 0xFFu) << 8) | ((aux & 3u) << 6) | (aux >> 2);

@@ -21,6 +21,7 @@
 #include "kq_device.h"
 #include "kq_partition.h"
 #include "kq_mem_host.h"
+#include "kq_plan_host.h"
 #include "kq_roff_host.h"
 #include "kq_seg_gate_host.h"
 #include "kq_select_host.h"
@@ -247,6 +248,8 @@ struct kq_handle {
     uint64_t reg_hi() const { return windowed ? (uint64_t)win_hi * (n_regions >> 8) : n_regions; }
     uint64_t n_alloc_regions() const { return reg_hi() - reg_lo(); }
     uint64_t n_slots() const { return n_alloc_regions() << REGION_SHIFT; }      // allocated slots
+    uint64_t table_bytes() const { return n_slots() * sizeof(Slot); }
+    TableShape shape() const { return TableShape{k, n_regions, map_count, mid_rps}; }      // what a partition plan depends on (kq_plan_host.h)
 };
 
 static void marks_reset(kq_handle* h);
@@ -337,9 +340,9 @@ static int check_errors(kq_handle* h) {
 static int grow_main(kq_handle* h, uint64_t need_slots) {
     int frc = flush_pending(h);          // pending records are sorted by the regions of the current geometry
     if (frc) return frc;
-    uint64_t want = h->n_slots(), new_regions = h->n_regions;       // doubling keeps every multiple the geometry (and a window) needs
-    while (want < need_slots) { want *= 2; new_regions *= 2; }
-    if (new_regions >= (1ull << 32)) return fail(KQ_ERR_TABLE_FULL, "cannot grow k-mer table to %llu slots: region index overflow", (unsigned long long)want);
+    const GrowTarget grown = grow_target(h->n_slots(), h->n_regions, need_slots);
+    const uint64_t want = grown.slots, new_regions = grown.regions;
+    if (!grown.ok) return fail(KQ_ERR_TABLE_FULL, "cannot grow k-mer table to %llu slots: region index overflow", (unsigned long long)want);
     // the new table in local owners; after the swap they hold the old one, which goes at scope exit on every way out: behind
     // the stream synchronisation below (the rehash reads it), or, if that fails, through a free that waits for the device
     DevMem slots, rstart;
@@ -369,7 +372,6 @@ static int grow_hc(kq_handle* h, uint64_t need) {
     return KQ_OK;
 }
 
-constexpr uint64_t HC_CAP_BIG = 1ull << 25;      // side-table floor of jobs beyond 2^31 instances (2.7 GB)
 // Make room for a batch that may add `extra` distinct k-mers and `extra_instances` instances.
 //  main table : load <= 0.85 even if every k-mer of the batch is new (unless the caller vouched for
 //               capacity_hint with KQ_OPT_TRUST_CAPACITY); host-side upper bounds avoid a device round trip.
@@ -379,12 +381,12 @@ static int reserve(kq_handle* h, uint64_t extra, uint64_t extra_instances) {
     int rc;
     bool state_read = false;
     if (!h->trust_capacity) {
-        uint64_t need = (uint64_t)((double)(h->used_bound + extra) / 0.85) + REGION_SLOTS;
+        uint64_t need = main_need(h->used_bound, extra);
         if (need > h->n_slots()) {
             rc = read_state(h); if (rc) return rc;
             state_read = true;
             h->used_bound = h->host_state()->slots_used;
-            need = (uint64_t)((double)(h->used_bound + extra) / 0.85) + REGION_SLOTS;
+            need = main_need(h->used_bound, extra);
             if (need > h->n_slots()) { rc = grow_main(h, need); if (rc) return rc; }
         }
     }
@@ -395,23 +397,14 @@ static int reserve(kq_handle* h, uint64_t extra, uint64_t extra_instances) {
     // number that reaches cov 255 halves): looked at once per doubling of the instance count here, and before every
     // table pass over pending records (flush_pending).  A side table that fills up anyway is reported as
     // KQ_ERR_TABLE_FULL by the next synchronising call
-    const uint64_t bound = h->kmers_bound / 255 + 1;
-    uint64_t need_hc = 2 * std::min<uint64_t>(bound, 1ull << 23);
-    if (bound > (1ull << 23)) need_hc = HC_CAP_BIG;
-    if (bound > (1ull << 23) && h->kmers_bound >= h->hc_check_at && h->n_pend == 0) {
+    uint64_t need_hc = hc_need(h->kmers_bound);
+    if (hc_follows_fill(h->kmers_bound) && h->kmers_bound >= h->hc_check_at && h->n_pend == 0) {
         if (!state_read) { rc = read_state_raw(h); if (rc) return rc; }
-        need_hc = std::max<uint64_t>(need_hc, 8 * h->host_state()->hc_used);
+        need_hc = hc_need(h->kmers_bound, h->host_state()->hc_used);
         h->hc_check_at = 2 * h->kmers_bound;
     }
     if (need_hc > h->hc_cap) { rc = grow_hc(h, need_hc); if (rc) return rc; }
     return KQ_OK;
-}
-
-// aligned view of a device byte string: 16-byte aligned base + lead
-static inline void aligned_view(const char* d, const uint8_t** ab, uint64_t* lead) {
-    uintptr_t p = (uintptr_t)d;
-    *lead = p & 15;
-    *ab = (const uint8_t*)(p - *lead);
 }
 
 static int stage_in(kq_handle* h, const void* host, size_t bytes, void** dev) {
@@ -491,20 +484,6 @@ int kq_device_memory(int device, uint64_t* free_bytes, uint64_t* total_bytes) {
     return KQ_OK;
 }
 
-// table geometry: region counts the record formats can address
-static uint64_t round_regions(uint64_t regions, int k) {
-    if (regions < 16) regions = 16;
-    // FMT_NARROW / FMT_TOP8 records: 256 hash-prefix buckets of whole regions; k >= HI_K needs it for every table
-    // (a slot drops the top 8 hash bits, which its region then implies)
-    if (regions >= (uint64_t)NB_MAX || k >= HI_K) regions = (regions + 255) / 256 * 256;
-    if (regions >= (1ull << 19)) {                                                  // ... of 2^s sub-buckets of whole regions each, <= 256 regions per sub-bucket
-        uint32_t sbits = 3;
-        while (sbits < SUB_BITS_MAX && (((regions + 255) / 256) >> sbits) > 256) ++sbits;
-        const uint64_t unit = 256ull << sbits;
-        regions = (regions + unit - 1) / unit * unit;
-    }
-    return regions;
-}
 // KQ_OPT_BUCKET_WINDOW: the (empty) table becomes the window [lo, hi) of the 256 hash-prefix buckets of a geometry that is
 // 256 / (hi - lo) times larger: the memory stays what kq_create sized, the handle then holds -- and answers for -- only
 // the k-mers of those buckets (a multi-GPU shard; kq_insert_sharded_dev / kq_insert_sharded8_dev bring them).
@@ -524,20 +503,16 @@ static int set_window(kq_handle* h, uint32_t lo, uint32_t hi, bool shard = false
         h->win_lo = lo; h->win_hi = hi;
         return KQ_OK;
     }
-    const uint64_t nb = hi - lo;
-    const uint64_t alloc_now = h->n_alloc_regions();
-    uint64_t virt = round_regions(std::max<uint64_t>((alloc_now + nb - 1) / nb * 256, (uint64_t)NB_MAX), h->k);
-    if (virt >= (1ull << 32)) return fail(KQ_ERR_INVALID, "bucket window too narrow for a table of %llu regions", (unsigned long long)alloc_now);
+    const WindowGeom g = window_geometry(h->n_alloc_regions(), lo, hi, h->k);
+    if (!g.ok) return fail(KQ_ERR_INVALID, "bucket window too narrow for a table of %llu regions", (unsigned long long)h->n_alloc_regions());
     HIPC(hipStreamSynchronize(h->stream));
     // the new table first: a failed allocation leaves the handle as it was
-    const bool windowed = !(lo == 0 && hi == 256);
-    const uint64_t alloc_new = windowed ? (uint64_t)(hi - lo) * (virt >> 8) : virt;
     DevMem slots, rstart;
-    int rc = alloc_main(h, virt, alloc_new, slots, rstart);
+    int rc = alloc_main(h, g.virt, g.alloc_new, slots, rstart);
     if (rc) return rc;
     HIPC(hipStreamSynchronize(h->stream));
     slots.swap(h->slots); rstart.swap(h->rstart);          // (the old table goes at scope exit)
-    h->n_regions = virt; h->win_lo = lo; h->win_hi = hi; h->windowed = windowed;
+    h->n_regions = g.virt; h->win_lo = lo; h->win_hi = hi; h->windowed = !(lo == 0 && hi == 256);
     h->slots_dirty = false;
     return KQ_OK;
 }
@@ -568,8 +543,7 @@ int kq_create(kq_handle** out, int device, int k, int map_count, uint64_t capaci
             rc = fail(KQ_ERR_NOMEM, "state allocation failed"); break;
         }
         (void)hipMemsetAsync(h->d_state(), 0, sizeof(DevState), h->stream);
-        uint64_t slots = (uint64_t)((double)(capacity_hint ? capacity_hint : (1u << 20)) / 0.7);   // load <= 0.7 at the hinted size
-        const uint64_t regions = round_regions((slots + REGION_SLOTS - 1) >> REGION_SHIFT, k);
+        const uint64_t regions = initial_regions(capacity_hint, k);
         rc = alloc_main(h, regions, regions, h->slots, h->rstart); if (rc) break;
         h->n_regions = regions;
         uint64_t hc = 1u << 16;
@@ -721,15 +695,9 @@ int kq_get_info(kq_handle* h, kq_info* out) {
 
 // ---- count ---------------------------------------------------------------------------------
 // ---- partitioned count: host orchestration -------------------------------------------------------
-struct PartPlan {
-    PartCfg cfg;              // P1 (bases -> coarse buckets)
-    bool two_level;
-    int fmt;                  // record format between the stages (FMT_*)
-    uint64_t n_max, R;
-    uint32_t g1;              // P1 scatter workgroups
+struct PartPlan : PlanSizes {   // the plan's numbers (kq_plan_host.h) ...
     bool even_buckets = false;   // the slice's bucket offsets were read back and passed kq::seg_gate_even (count_partitioned)
-    uint64_t m1_n, m2_n, sums_n, groups_n;
-    // device pointers into h->work
+    // ... and its device pointers into h->work
     uint64_t *recs1, *recs2;
     uint8_t *aux1, *aux2;     // WIDE records: edge bytes travelling with recs1 / recs2
     unsigned long long *m1, *seg_off, *unit_base, *group_base, *sums, *total, *hot;
@@ -738,77 +706,29 @@ struct PartPlan {
     uint8_t* a1() const { return fmt == FMT_WIDE || fmt == FMT_NARROW ? aux1 : nullptr; }
     uint8_t* a2() const { return fmt == FMT_WIDE || fmt == FMT_NARROW ? aux2 : nullptr; }
 };
-static void plan_cfg(const kq_handle* h, PartCfg* cfg, bool allow_narrow = false) {
-    cfg->n_regions = h->n_regions;
-    // fan-outs: the first split (fused with the sequence scan) is insensitive to its fan-out up to
-    // ~512 bins, the second is bound by the length of the runs it writes (4096 / fan-out records), so
-    // the first level takes as many bins as it can: 256..512 coarse buckets, the rest in level two
-    // (measured on configs[1]: 262 x 64 beats the balanced 66 x 256 by 0.2 ms per 130 M records)
-    uint32_t g = 1;
-    while (((cfg->n_regions + (1ull << g) - 1) >> g) > 512 && g < 10) ++g;
-    while (((cfg->n_regions + (1ull << g) - 1) >> g) >= (uint64_t)NB_MAX) ++g;
-    cfg->g_shift = cfg->n_regions < (uint64_t)NB_MAX ? 0 : g;
-    cfg->n_coarse = (uint32_t)((cfg->n_regions + (1ull << cfg->g_shift) - 1) >> cfg->g_shift);
-    cfg->mode = 0; cfg->map_count = (uint32_t)h->map_count;
-    cfg->map_mask = (h->map_count & (h->map_count - 1)) == 0 ? (uint32_t)h->map_count - 1 : 0;
-    cfg->filt_lo = 0; cfg->filt_hi = (uint32_t)h->map_count;
-    cfg->raw_out = 0;
-    // 5-byte records (FMT_NARROW): first split on the top 8 hash bits, which needs every bucket to own a
-    // whole number of regions (kq_create rounds large tables to a multiple of 256 regions; doubling keeps it)
-    cfg->narrow = 0; cfg->sub_bits = 0; cfg->owner_sub = 0; cfg->n_rng = 0; cfg->win_lo = 0; cfg->win_hi = 1u << NARROW_CBITS;
-    if (allow_narrow && (h->k <= (int)NARROW_MAX_K || h->k > PART_MAX_K) && cfg->n_regions >= (uint64_t)NB_MAX && cfg->n_regions % (1u << NARROW_CBITS) == 0) {
-        const uint64_t rps = cfg->n_regions >> NARROW_CBITS;
-        // one level bucket -> regions while a bucket has < mid_rps regions (the multisplit writes runs of 4096 / fan-out
-        // records, so the last fan-out should stay near 256), else a middle level of 2^sb sub-buckets (sb <= 8): covers
-        // every table that fits the HBM.  kq_create rounds the region count so that sb reaches its target
-        uint32_t sb = 0;
-        if (rps >= h->mid_rps) {
-            const uint64_t target_nb = std::max<uint64_t>(1, std::min<uint64_t>(256, h->mid_rps / 8));
-            while ((rps >> sb) > target_nb && sb < SUB_BITS_MAX && rps % (2ull << sb) == 0) ++sb;
-        }
-        if ((rps >> sb) < (uint64_t)NB_MAX && (sb > 0 || rps < (uint64_t)NB_MAX)) { cfg->narrow = 1; cfg->sub_bits = sb; }
-    }
-    if (cfg->narrow) { cfg->n_coarse = 1u << NARROW_CBITS; if (cfg->g_shift == 0) cfg->g_shift = 1; }
-}
-// carve the scratch buffer for a batch of at most n_max records; n_tiles = 0 when the input is records
+// carve the scratch buffer for a batch of at most n_max records (plan_sizes / plan_layout: kq_plan_host.h); n_tiles = 0 when
+// the input is records
 static int plan_alloc(kq_handle* h, PartPlan* p, uint64_t n_max, uint64_t n_tiles, uint32_t p1_bins, bool allow_narrow = false,
                       uint64_t min_segs = 0 /*segments / output groups an exchange level needs beyond the table's own*/) {
     if (h->test_fail_plan) { h->test_fail_plan = false; return fail(KQ_ERR_NOMEM, "partition scratch allocation failed (injected by KQ_OPT_TEST_FAIL_PLAN)"); }
     if (n_max >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "a partition pass handles fewer than 2^32 records (got %llu): slice the input", (unsigned long long)n_max);
-    plan_cfg(h, &p->cfg, allow_narrow);
-    n_max = (n_max + 7) & ~7ull;                                // every record array starts 16-byte aligned and has slack for vector loads
-    p->two_level = p->cfg.g_shift != 0;
-    p->fmt = !p->cfg.narrow ? FMT_PACK8 : h->k > PART_MAX_K ? FMT_TOP8 : FMT_NARROW;      // the caller switches to FMT_WIDE where it applies
-    p->n_max = n_max; p->R = p->cfg.n_regions;
-    // scatter workgroups: six times what is resident (3 or 2 per CU), each with its own cursor column: the hardware
-    // dispatcher balances them (a grid of exactly the resident count ran 8 % longer: k_p1_scatter 577 -> 531 us)
-    p->g1 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, (uint64_t)h->n_cu * (p1_bins < 512 ? 18 : 12)));
-    p->m1_n = (uint64_t)p1_bins * p->g1 * P1_F;
-    const uint64_t nb_max = std::max<uint64_t>(std::max<uint64_t>(1ull << p->cfg.g_shift, p->cfg.n_coarse), p->cfg.narrow ? (p->cfg.n_regions >> NARROW_CBITS) >> p->cfg.sub_bits : 0);
-    const uint64_t seg_max = std::max<uint64_t>(min_segs, p->cfg.narrow ? ((uint64_t)1 << NARROW_CBITS) << p->cfg.sub_bits : (uint64_t)NB_MAX);      // segments of the widest level
-    p->m2_n = (n_max / P2_UNIT + seg_max + 2) * nb_max;         // u32 entries, enough for either level
-    p->groups_n = std::max<uint64_t>(std::max<uint64_t>(p->R, (uint64_t)p->cfg.n_coarse << p->cfg.g_shift), min_segs) + 2;
-    p->sums_n = std::max(p->m1_n, p->groups_n) / SCAN_CHUNK + 2;
-    const uint64_t aux_words = (n_max + 7) / 8 + 1;
-    const uint64_t rec_words = p->fmt == FMT_NARROW ? n_max / 2 + 2 : n_max;          // narrow records: u32 + lockstep byte
+    static_cast<PlanSizes&>(*p) = plan_sizes(h->shape(), h->n_cu, n_max, n_tiles, p1_bins, allow_narrow, min_segs);
+    const PlanLayout at = plan_layout(*p);
     // the second record array of a large plan lives in a physically scrambled buffer of its own (struct Scrambled)
-    const bool split2 = (rec_words + aux_words) * 8 >= ((size_t)512 << 20);
-    if (split2) { int rc2 = scr_ensure(h->work.part2, (size_t)(rec_words + aux_words) * 8, h->device); if (rc2) return rc2; }
-    const size_t words = (size_t)((split2 ? 1 : 2) * (rec_words + aux_words) + p->m1_n + 2 * (seg_max + 2) + p->groups_n + p->sums_n + 4 + (p->R + 2) + (p->m2_n + 1) / 2);
-    HIPC(h->work.part.ensure(words * 8));
-    p->recs1 = h->work.part.as<uint64_t>();
-    p->aux1 = (uint8_t*)(p->recs1 + rec_words);
-    uint64_t* rest = (uint64_t*)(p->aux1 + aux_words * 8);
-    if (split2) { p->recs2 = (uint64_t*)h->work.part2.p; p->aux2 = (uint8_t*)(p->recs2 + rec_words); }
-    else { p->recs2 = rest; p->aux2 = (uint8_t*)(p->recs2 + rec_words); rest = (uint64_t*)(p->aux2 + aux_words * 8); }
-    p->m1 = (unsigned long long*)rest;
-    p->seg_off = p->m1 + p->m1_n;
-    p->unit_base = p->seg_off + seg_max + 2;
-    p->group_base = p->unit_base + seg_max + 2;
-    p->sums = p->group_base + p->groups_n;
-    p->total = p->sums + p->sums_n;
-    p->hot = p->total + 4;
-    p->m2 = (uint32_t*)(p->hot + p->R + 2);
+    if (p->split2) { int rc2 = scr_ensure(h->work.part2, at.part2_bytes, h->device); if (rc2) return rc2; }
+    HIPC(h->work.part.ensure((size_t)at.words * 8));
+    uint64_t* const base = h->work.part.as<uint64_t>();
+    uint64_t* const base2 = p->split2 ? (uint64_t*)h->work.part2.p : base;
+    p->recs1 = base + at.recs1; p->aux1 = (uint8_t*)(base + at.aux1);
+    p->recs2 = base2 + at.recs2; p->aux2 = (uint8_t*)(base2 + at.aux2);
+    p->m1 = (unsigned long long*)(base + at.m1);
+    p->seg_off = (unsigned long long*)(base + at.seg_off);
+    p->unit_base = (unsigned long long*)(base + at.unit_base);
+    p->group_base = (unsigned long long*)(base + at.group_base);
+    p->sums = (unsigned long long*)(base + at.sums);
+    p->total = (unsigned long long*)(base + at.total);
+    p->hot = (unsigned long long*)(base + at.hot);
+    p->m2 = (uint32_t*)(base + at.m2);
     return KQ_OK;
 }
 // exclusive scan of n u64 on the device (in place); *total (device) receives the sum
@@ -920,13 +840,6 @@ static int run_p1(kq_handle* h, PartPlan* p, const PartCfg& cfg, const uint8_t* 
 struct LevelIn { const uint64_t* recs; const uint8_t* aux; const unsigned long long *seg_lo, *seg_hi; uint32_t n_seg, spb; };
 // records grouped by the plan's own segment table p.seg_off[0..n_seg]: every segment ends where the next one starts
 static LevelIn own_segments(const PartPlan& p, const uint64_t* recs, const uint8_t* aux, uint32_t n_seg) { return LevelIn{recs, aux, p.seg_off, p.seg_off + 1, n_seg, 1}; }
-// rank replication of a level's bin counters: as many counters per bin as fit 512 (at most 64, one per lane)
-static LevelCfg with_rep_shift(const LevelCfg& lv) {
-    LevelCfg lvr = lv;
-    lvr.rep_shift = 0;
-    while (lvr.rep_shift < 6 && (((uint64_t)lv.nb + 1) << (lvr.rep_shift + 1)) <= 512) ++lvr.rep_shift;
-    return lvr;
-}
 // what the unit kernels of a level read: the input records and segments, the level and the unit table
 struct LevelUnits { const uint64_t* in; const uint8_t* in_aux; LevelCfg lv; const unsigned long long *seg_lo, *seg_hi, *unit_base; uint32_t* m2; unsigned grid; };
 static int launch_level_hist(kq_handle* h, const KernelSel& s, const LevelUnits& u) {
@@ -973,38 +886,6 @@ static void run_segment_level(kq_handle* h, PartPlan* p, const LevelCfg& lv, con
     hipLaunchKernelGGL(k_lv_segment_s, dim3(lv.n_seg), dim3(LV_THREADS), 0, h->stream, (const uint32_t*)in, in_aux, with_rep_shift(lv), p->seg_off, gb, (uint32_t*)out);
     mark(h, "k_lv_scatter");
 }
-static LevelCfg level_coarse_to_regions(const PartCfg& cfg) {
-    LevelCfg lv; lv.n_regions = cfg.n_regions; lv.n_seg = cfg.n_coarse; lv.nb = 1u << cfg.g_shift; lv.seg_shift = cfg.g_shift; lv.out_shift = 0; lv.in_raw = 0; lv.k = 0; lv.narrow = 0; lv.top8 = 0;
-    lv.nr_shift = lv.nr_rps = lv.nr_sub = lv.nr_inv = 0; lv.nr_div = 1;
-    lv.nr_mid = 0; lv.nr_fshift = 24; lv.nr_fmask = 0xFFFFFFu; lv.nr_f24 = 0;
-    lv.spb = 1;
-    return lv;
-}
-// FMT_NARROW: 256 top-bit buckets -> their regions (bucket b owns regions [b * nb, (b + 1) * nb))
-// `sub_bits` > 0: a middle level first cuts every bucket into 2^sub_bits sub-buckets (tables of more than
-// 2048 regions per bucket: the last level then has 256 << sub_bits segments of rps >> sub_bits regions)
-static LevelCfg level_narrow(const PartCfg& cfg, uint32_t sub_bits = 0, bool middle = false, bool top8_records = false) {
-    LevelCfg lv; lv.n_regions = cfg.n_regions;
-    const uint32_t rps = (uint32_t)(cfg.n_regions >> NARROW_CBITS), subsz = rps >> sub_bits;
-    lv.seg_shift = 0; lv.out_shift = 0; lv.in_raw = 0; lv.k = 0; lv.narrow = top8_records ? 2 : 1; lv.top8 = 0;
-    lv.nr_rps = rps; lv.nr_sub = subsz;
-    if (middle) { lv.n_seg = 1u << NARROW_CBITS; lv.nb = 1u << sub_bits; lv.nr_shift = 0; lv.nr_div = subsz; }
-    else        { lv.n_seg = (1u << NARROW_CBITS) << sub_bits; lv.nb = subsz; lv.nr_shift = sub_bits; lv.nr_div = 1; }
-    lv.nr_inv = lv.nr_div > 1 ? (uint32_t)(((1ull << 32) + lv.nr_div - 1) / lv.nr_div) : 0;
-    lv.nr_mid = middle ? 1u : 0u; lv.nr_fshift = 24 - sub_bits; lv.nr_fmask = (1u << (24 - sub_bits)) - 1u;
-    lv.nr_f24 = ((uint64_t)subsz << (24 - sub_bits)) <= (1ull << 32) && subsz < (1u << 24) ? 1u : 0u;
-    lv.spb = 1;
-    return lv;
-}
-// FMT_TIGHT output of the last split level (count path only: the lookup kernels read 5-byte records)
-static bool tight_ok(const kq_handle* h, const PartPlan& p) { return p.fmt == FMT_NARROW && p.R >= TIGHT_MIN_REGIONS && (bool)h->rstart; }
-static LevelCfg level_flat_to_coarse(const PartCfg& cfg) {
-    LevelCfg lv; lv.n_regions = cfg.n_regions; lv.n_seg = 1; lv.nb = cfg.n_coarse; lv.seg_shift = 32; lv.out_shift = cfg.g_shift; lv.in_raw = 0; lv.k = 0; lv.narrow = 0; lv.top8 = 0;
-    lv.nr_shift = lv.nr_rps = lv.nr_sub = lv.nr_inv = 0; lv.nr_div = 1;
-    lv.nr_mid = 0; lv.nr_fshift = 24; lv.nr_fmask = 0xFFFFFFu; lv.nr_f24 = 0;
-    lv.spb = 1;
-    return lv;
-}
 // ---- pending sets ---------------------------------------------------------------------------------
 // A k_count_regions pass streams every region image of the table in and out once, whatever the number of records it
 // applies.  So the region-sorted record set that P1 + the split levels make of a slice is not applied at once: it is
@@ -1015,17 +896,6 @@ static LevelCfg level_flat_to_coarse(const PartCfg& cfg) {
 // per slice; KQ_OPT_PENDING_BYTES bounds the arena (0 = apply every slice at once, the round-1 behaviour).
 __global__ void k_p3set(P3Set* sets, int i, P3Set v) { sets[i] = v; }
 
-// layout of one pending set of at most n_max records: the records, their lockstep bytes (formats that have them), R + 2 region offsets
-struct SetLayout { bool has_aux; size_t aux_off /*= the record bytes*/, base_off, total; };
-static SetLayout set_bytes(uint64_t n_max, int fmt, uint64_t R) {
-    const size_t rec = (fmt == FMT_NARROW || fmt == FMT_TIGHT) ? 4 : 8;
-    SetLayout l;
-    l.has_aux = fmt == FMT_NARROW || fmt == FMT_WIDE;
-    l.aux_off = ((size_t)n_max * rec + 63) & ~(size_t)63;
-    l.base_off = l.aux_off + (l.has_aux ? ((size_t)n_max + 63) & ~(size_t)63 : 0);
-    l.total = (l.base_off + (size_t)(R + 2) * 8 + 255) & ~(size_t)255;
-    return l;
-}
 // Where the last split level writes records, lockstep bytes and region offsets: a pending set in the arena (recs != nullptr) or
 // the plan's scratch, whose set is applied at once (the scratch is reused by the next slice).  fmt / aux_fmt: of the finished
 // set; `tight`: the last level writes FMT_TIGHT records (count path only: the lookup kernels read 5-byte records)
@@ -1047,23 +917,13 @@ static int arena_take(kq_handle* h, uint64_t n_max, uint64_t R, Dest* d) {
         int rc = flush_pending(h);
         if (rc) return rc;
     }
-    // The arena starts at a few sets and doubles every time it fills up, up to a few times the table and what is free less
-    // a reserve (a fixed KQ_OPT_PENDING_BYTES is taken as it is): a short job never pays for allocating tens of GB (hipMalloc
-    // costs milliseconds per GB), a long one gets there within its first batches
-    size_t want = h->arena_bytes;
-    if (need > want) want = h->pend_budget > 0 ? (size_t)h->pend_budget : std::max<size_t>(4 * need, (size_t)64 << 20);
-    else if (was_full && h->pend_budget < 0) want = 2 * h->arena_bytes;
+    // the arena grows as arena_want / arena_budget say (kq_plan_host.h)
+    const size_t want = arena_want(need, h->arena_bytes, was_full, h->pend_budget);
     if (want > h->arena_bytes) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return KQ_OK;
-        size_t budget = want;
-        // ceiling: what is free now (the partition scratch of this slice size is allocated already) less a reserve of 1/8 of
-        // the device for whatever comes later (side-table growth, lookup / export buffers); half of it when that is tight
-        const size_t avail = free_b + h->arena_bytes, reserve = std::max<size_t>(total_b / 8, (size_t)8 << 30);
-        const size_t ceiling = avail > 2 * reserve ? avail - reserve : avail / 2;
-        if (h->pend_budget < 0) budget = std::min<size_t>(want, std::min<size_t>(ceiling, std::max<size_t>(4 * need, 4 * (size_t)h->n_slots() * sizeof(Slot))));
-        if (budget <= h->arena_bytes && need <= h->arena_bytes) budget = 0;         // at its ceiling already
-        if (budget && budget < need) return KQ_OK;
+        const size_t budget = arena_budget(want, need, h->arena_bytes, h->pend_budget, free_b, total_b, (size_t)h->table_bytes());
+        if (budget == ARENA_STAY) return KQ_OK;
         if (budget) {
             if (h->arena.p) { HIPC(hipStreamSynchronize(h->stream)); HIPC(hipStreamSynchronize(h->base)); h->arena.reset(); h->arena_bytes = 0; }
             static const bool scramble_arena = !getenv("KQ_SCRAMBLE_ARENA") || atoi(getenv("KQ_SCRAMBLE_ARENA")) != 0;      // (0: plain hipMalloc, for A/B)
@@ -1135,9 +995,9 @@ static int flush_pending_base(kq_handle* h) {
     const uint64_t R = h->n_regions;
     HIPC(h->hot.ensure((size_t)(R + 2) * 8));
     int rc;
-    if (h->kmers_bound / 255 + 1 > (1ull << 23)) {       // large jobs: the side table follows its observed fill (see reserve)
+    if (hc_follows_fill(h->kmers_bound)) {       // large jobs: the side table follows its observed fill (see reserve)
         rc = read_state_raw(h); if (rc) return rc;
-        const uint64_t need_hc = std::max<uint64_t>(HC_CAP_BIG, 8 * h->host_state()->hc_used);
+        const uint64_t need_hc = hc_need(h->kmers_bound, h->host_state()->hc_used);
         if (need_hc > h->hc_cap) { rc = grow_hc(h, need_hc); if (rc) return rc; }
     }
     unsigned long long* hot = h->hot.as<unsigned long long>();     // [0] = count, then up to R region ids
@@ -1184,18 +1044,10 @@ static int flush_pending_base(kq_handle* h) {
     return KQ_OK;
 }
 
-// can the record split reach every region of this table?  (5-byte records: up to 256 x 8 x 2047 regions, i.e.
-// any table that fits the HBM; 8-byte / wide records: two fan-outs below NB_MAX)
-static bool part_table_ok(const kq_handle* h, bool narrow_possible) {
-    if (h->n_regions <= (1ull << 20)) return true;
-    if (!narrow_possible) return false;
-    PartCfg c; plan_cfg(h, &c, true);
-    return c.narrow != 0;
-}
 // the destination of the set the plan's levels make of at most n_max records: in the arena if it has (or gets) room, else the
 // scratch.  (A map-range pass calls this after P1, with the record count P1 found: see count_partitioned)
 static int dest_take(kq_handle* h, const PartPlan& p, uint64_t n_max, Dest* d) {
-    d->tight = tight_ok(h, p);
+    d->tight = tight_ok(p.fmt, p.R, (bool)h->rstart);
     if (d->tight) { d->fmt = FMT_TIGHT; d->aux_fmt = AUX_TIGHT; }
     return arena_take(h, n_max, p.R, d);
 }
@@ -1257,13 +1109,11 @@ static int sort_and_submit(kq_handle* h, PartPlan* p, const LevelIn& in, const D
     return rc ? rc : submit(h, set, d);
 }
 
-// the plan of a scanned sequence (count, region-wise lookup): 5-byte records up to k = 21 and 8-byte hash-remainder records
-// above k = 28 (tables with hash-prefix buckets), 8-byte packed records up to k = 28, hash + edge byte otherwise
+// the plan of a scanned sequence (count, region-wise lookup), in the record format sequence_fmt gives it
 static int plan_sequence(kq_handle* h, PartPlan* p, uint64_t lead, uint64_t len) {
-    PartCfg c0; plan_cfg(h, &c0, true);
-    int rc = plan_alloc(h, p, len, n_tiles_of(lead, len), c0.n_coarse, true);
+    int rc = plan_alloc(h, p, len, n_tiles_of(lead, len), plan_cfg(h->shape(), true).n_coarse, true);
     if (rc) return rc;
-    if (h->k > PART_MAX_K && p->fmt != FMT_TOP8) p->fmt = FMT_WIDE;
+    p->fmt = sequence_fmt(p->fmt, h->k);
     return KQ_OK;
 }
 
@@ -1330,55 +1180,16 @@ static int count_partitioned_records(kq_handle* h, const uint64_t* d_recs, const
     return sort_and_submit(h, &p, coarse, dst);
 }
 
-// the k-mer starts [a, b) of a resident sequence as a scan of their own (the margins: see count_seq_dev): ASCII bytes
-// (d_inv == nullptr) or the packed form, whose words hold 16 bases
-struct SliceView { const uint8_t* ab; const uint16_t* pinv; uint64_t lead, len; EmitRange er; };
-static SliceView slice_view(const char* d_bases, const uint16_t* d_inv, uint64_t len, int k, uint64_t a, uint64_t b) {
-    const uint64_t sub_off = a ? a - 1 : 0;
-    SliceView v;
-    v.len = std::min(len, b + k) - sub_off;
-    v.er = EmitRange{a - sub_off, b - sub_off};
-    v.pinv = nullptr;
-    if (d_inv) { v.ab = (const uint8_t*)(reinterpret_cast<const uint32_t*>(d_bases) + sub_off / 16); v.pinv = d_inv + sub_off / 16; v.lead = sub_off % 16; }
-    else aligned_view(d_bases + sub_off, &v.ab, &v.lead);
-    return v;
-}
-
 // count a resident sequence: ASCII bytes (d_inv == nullptr) or the packed form (d_bases = the code words, d_inv = the masks)
 static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_inv, uint64_t len) {
     if (!h || (!d_bases && len)) return fail(KQ_ERR_INVALID, "null argument");
     HIPC(hipSetDevice(h->device));
     if (len < (uint64_t)h->k) return KQ_OK;                                  // src/graph-builder.cpp:60
     const uint64_t kmers = len - h->k + 1;
-    // a resident batch of any size is processed in slices of <= 2^28 k-mer starts (the partition
-    // scratch is 16 B per start); a slice scans one extra base on the left and k on the right, so
-    // k-mers and edges across a cut are seen exactly once
-    // Without pending sets (KQ_OPT_PENDING_BYTES = 0) the partitioned path streams the whole table once per slice, so a
-    // slice should bring a few records per slot: with a large table (and memory to spare for 16 B of scratch per start)
-    // slices grow up to 2^31 starts.  With pending sets the table pass is shared by many slices and the default holds.
-    uint64_t slice = h->slice_kmers;
-    if (h->pend_budget != 0 && !h->slice_user && kmers > slice) {
-        // large tables split records over up to 65536 segments before the last level: slices of up to 2^31 starts keep
-        // a few work units per segment and the number of pending sets per table pass low (one slice instead of two per
-        // 1.3e9-k-mer batch: table pass -3 %, step -1.8 % at 1000 Mbp); 10 B of scratch per start for the default k, so
-        // only as far as a quarter of the free HBM pays for it
-        const uint64_t base_slice = slice;
-        for (uint64_t cap : {1ull << 31, 1ull << 30}) {
-            slice = std::min<uint64_t>(cap, std::max<uint64_t>(base_slice, h->n_slots() / 4));
-            const uint64_t n_slices = (kmers + slice - 1) / slice;
-            slice = (kmers + n_slices - 1) / n_slices;           // equal slices
-            size_t free_b = 0, total_b = 0;
-            if (cap == (1ull << 30) || slice <= (1ull << 30)) break;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + h->work.part.bytes() >= (size_t)11 * slice + ((size_t)2 << 30)) break;   // the plan takes ~10.2 B per start
-        }
-    }
-    if (h->pend_budget == 0 && !h->slice_user && kmers > slice && 2 * h->n_slots() > slice) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t by_mem = (uint64_t)((free_b + h->work.part.bytes()) / 24);          // 16 B scratch + margin per start
-            slice = std::max(slice, std::min<uint64_t>(std::min<uint64_t>(2 * h->n_slots(), 1ull << 31), by_mem));
-        }
-    }
+    // slices (choose_slice, kq_plan_host.h); the device is asked for its free memory only where the choice depends on it
+    size_t free_b = 0, total_b = 0;
+    const bool have_mem_info = slice_reads_free(kmers, h->slice_kmers, h->slice_user, h->pend_budget, h->n_slots()) && hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    const uint64_t slice = choose_slice(kmers, h->slice_kmers, h->slice_user, h->pend_budget, h->n_slots(), free_b, h->work.part.bytes(), have_mem_info);
     // Fork / join: with two or more slices in this call, consecutive slices alternate between two internal streams (and two
     // scratch sets), both behind the caller's position on `base` (the input is ready there), and `base` is joined with them
     // before the call returns -- the caller's stream-ordered view of the handle does not change, and no fork outlives a call.
@@ -1387,10 +1198,7 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
         void leave() { if (swapped) { std::swap(h->work, h->fork_work); swapped = false; } h->stream = h->base; }
         ~ForkGuard() { leave(); (void)join_forks(h); }
     } guard{h};
-    // (not in a map-range pass: its slices read their record count back, and measured at full size the kernels of two such
-    // slices only time-slice the GPU -- no gain for a second scratch set taken from the arena)
-    const bool forked = h->overlap && !h->profile && h->count_path != 1 && (kmers + slice - 1) / slice >= 2 && slice >= (1u << 20) &&
-                        (h->overlap == 2 || (h->filt_lo == 0 && h->filt_hi == (uint32_t)h->map_count && !h->windowed));
+    const bool forked = slices_fork(h->overlap, h->profile, h->count_path, kmers, slice, h->filt_lo == 0 && h->filt_hi == (uint32_t)h->map_count && !h->windowed);
     if (forked) {
         for (int w = 0; w < 2; ++w) if (!h->fork_stream[w]) HIPC(h->fork_stream[w].create(hipStreamNonBlocking));
         hipEvent_t e_in; int erc = ev_get(h, &e_in); if (erc) return erc;
@@ -1403,21 +1211,11 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
         int rc = reserve(h, b - a, b - a);
         if (rc) return rc;
         const SliceView v = slice_view(d_bases, d_inv, len, h->k, a, b);
-        // a table pass streams the whole table (2 x 16 B per slot) on top of ~37 B per record; the atomic path costs
-        // ~95 ps per record whatever the table size (~480 B at the part's streaming rate): partition unless the table
-        // is more than ~200 B per record the pass will apply -- this slice, plus what is pending already, times the
-        // slices of this size the arena can still take (at most 8: the caller may read the table any time)
-        double pass_records = (double)(b - a);
-        if (h->pend_budget != 0) {
-            const double per_set = (double)set_bytes(b - a, FMT_PACK8, h->n_regions).total;
-            const double room = h->arena.p ? (double)h->arena_bytes : 4.0 * (double)h->n_slots() * sizeof(Slot);
-            pass_records = (double)h->pend_records + (double)(b - a) * std::max(1.0, std::min(8.0, room / per_set));
-        }
-        bool part = (b - a) >= (1u << 20) && part_table_ok(h, true) &&
-                    (double)h->n_slots() * sizeof(Slot) <= 200.0 * pass_records;
+        const bool table_ok = part_table_ok(h->shape(), true);
+        bool part = slice_partitions(b - a, table_ok, h->table_bytes(), h->n_regions, h->pend_budget, h->pend_records, h->arena.p != nullptr, h->arena_bytes);
         if (h->count_path == 1) part = false;
         if (h->count_path == 2) {
-            if (!part_table_ok(h, true)) return fail(KQ_ERR_INVALID, "table too large for the partitioned path");
+            if (!table_ok) return fail(KQ_ERR_INVALID, "table too large for the partitioned path");
             part = true;
         }
         if (part) {
@@ -1434,7 +1232,7 @@ static int count_seq_dev(kq_handle* h, const char* d_bases, const uint16_t* d_in
             continue;
         }
         if (forked) { rc = join_forks(h); if (rc) return rc; }       // the direct kernel updates the table: behind everything in flight
-        PartCfg filt; plan_cfg(h, &filt);
+        PartCfg filt = plan_cfg(h->shape());
         filt.filt_lo = h->filt_lo; filt.filt_hi = h->filt_hi;
         materialize(h);
         h->table_empty = false;
@@ -1754,9 +1552,7 @@ static int owner_split(kq_handle* h, const char* d_bases, uint64_t len, int n_pa
     const uint8_t* ab; uint64_t lead;
     aligned_view(d_bases, &ab, &lead);
     PartPlan p;
-    // up to 256 bins in all: owner part x sub-bin by lane (the order inside a part is unspecified anyway)
-    uint32_t sb = 0;
-    while (((uint32_t)n_parts << (sb + 1)) <= 256u && sb < 5) ++sb;
+    const uint32_t sb = owner_sub_bits(n_parts);
     const uint32_t bins = (uint32_t)n_parts << sb;
     int rc = plan_alloc(h, &p, 0, n_tiles_of(lead, len), bins);
     if (rc) return rc;
@@ -1796,8 +1592,7 @@ __global__ void k_sharded_segments(const unsigned long long* __restrict__ start 
     seg_hi[b * n_peers + q] = start[j] + counts[j];
 }
 
-// first bucket of part p of n_parts: the parts are contiguous ranges of the 256 hash-prefix buckets (kreeq_amd/dist.py: bucket_range)
-static inline uint32_t part_first_bucket(int p, int n_parts) { return (uint32_t)(((uint64_t)p * 256 + n_parts - 1) / n_parts); }
+// (the parts are contiguous ranges of the 256 hash-prefix buckets: part_first_bucket, kq_plan_host.h)
 __global__ void k_bucket_meta(const unsigned long long* __restrict__ seg_off, uint32_t n_parts, unsigned long long* __restrict__ counts) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_parts << NARROW_CBITS) return;
@@ -1850,8 +1645,7 @@ static int insert_buckets(kq_handle* h, const uint64_t* d_recs, const uint8_t* d
     if (!n) return KQ_OK;
     if (n >= (1ull << 32) - 16) return fail(KQ_ERR_INVALID, "a partition pass handles fewer than 2^32 records (got %llu)", (unsigned long long)n);
     if (!five) {   // the format of the plan the table allows, before anything is reserved or grown for records it cannot take
-        PartCfg c; plan_cfg(h, &c, true);
-        if (!c.narrow) return fail(KQ_ERR_INVALID, "the table has no hash-prefix bucket split for 8-byte hash-remainder records (fewer than 2048 regions): use kq_insert_records_dev");
+        if (!plan_cfg(h->shape(), true).narrow) return fail(KQ_ERR_INVALID, "the table has no hash-prefix bucket split for 8-byte hash-remainder records (fewer than 2048 regions): use kq_insert_records_dev");
     }
     int rc = reserve(h, n, n);
     if (rc) return rc;
@@ -1902,7 +1696,7 @@ int kq_insert_packed_dev(kq_handle* h, const uint64_t* d_recs, uint64_t n) {
     if (!n) return KQ_OK;
     int rc = reserve(h, n, n);
     if (rc) return rc;
-    if (!part_table_ok(h, true)) return fail(KQ_ERR_INVALID, "table too large for the partitioned path");
+    if (!part_table_ok(h->shape(), true)) return fail(KQ_ERR_INVALID, "table too large for the partitioned path");
     return count_partitioned_records(h, d_recs, nullptr, AUX_IDX6, n, false);
 }
 
@@ -2029,11 +1823,9 @@ int kq_lookup_sequence_dev(kq_handle* h, const char* d_bases, uint64_t len, uint
     const uint32_t map_mask = (h->map_count & (h->map_count - 1)) == 0 ? (uint32_t)h->map_count - 1 : 0;
     { int frc = flush_pending(h); if (frc) return frc; }
     materialize(h);
-    // counters only, a sequence worth partitioning, and a table small enough next to it (the partitioned path
-    // streams the whole table once per slice): regions staged in LDS instead of one random sector per k-mer
+    // the partitioned path (lookup_partitions): regions staged in LDS instead of one random sector per k-mer
     const uint64_t kmers = len - h->k + 1;
-    if (!d_per_base && h->lookup_path != 1 && part_table_ok(h, true) &&
-        (h->lookup_path == 2 || (kmers >= (1u << 20) && (double)h->n_slots() * sizeof(Slot) <= 64.0 * (double)std::min<uint64_t>(kmers, h->slice_kmers)))) {
+    if (lookup_partitions(d_per_base != nullptr, h->lookup_path, part_table_ok(h->shape(), true), kmers, h->slice_kmers, h->table_bytes())) {
         for (uint64_t a = 0; a < kmers; a += h->slice_kmers) {
             const uint64_t b = std::min(kmers, a + h->slice_kmers);
             const SliceView v = slice_view(d_bases, nullptr, len, h->k, a, b);

@@ -43,7 +43,7 @@ def owner_of(keys, world, map_count):
 
 
 def bucket_range(rank, world):
-    """hash-prefix buckets owned by `rank` -- must match part_first_bucket() in csrc/kreeq_amd.hip"""
+    """hash-prefix buckets owned by `rank` -- must match part_first_bucket() in csrc/kq_plan_host.h"""
     return -(-rank * 256 // world), -(-(rank + 1) * 256 // world)
 
 

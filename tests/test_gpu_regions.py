@@ -44,7 +44,7 @@ def O():
 
 
 def n_regions_of(k, cls):
-    """region count kq_create gives the class (kreeq_amd.hip kq_create / round_regions: load 0.7 at the hint, whole
+    """region count kq_create gives the class (kq_plan_host.h initial_regions / round_regions: load 0.7 at the hint, whole
     multiples of 256 regions from 2048 on and for k >= 29); asserted against info() on every handle"""
     r = max(16, -(-int((HINT[cls] or 1 << 20) / 0.7) // FULL))
     return -(-r // 256) * 256 if r >= 2048 or k >= 29 else r
