@@ -259,6 +259,46 @@ int  kq_parse_fastx_dev(kq_handle* h, const char* d_text, uint64_t len, int form
 int  kq_count_fastx_dev(kq_handle* h, const char* d_text, uint64_t len, int format);
 int  kq_count_fastx_async(kq_handle* h, const char* text, uint64_t len, int format, uint64_t* ticket);
 
+/* BGZF-compressed reads (the block-gzip container of bgzip / htslib: valid multi-member gzip in which every member is an
+ * independent DEFLATE stream of at most 64 KiB in and 64 KiB out, with its compressed size in the header's 'BC' extra subfield
+ * and CRC-32 + ISIZE in the trailer).  The compressed bytes go to the GPU, one member per wave is inflated there, and the text
+ * feeds the device parser above: no text touches the host.  Plain single-member gzip is not handled here.
+ *   kq_bgzf_scan         host only, no device: walks members from data[0].  A member is accepted iff ID1 ID2 CM FLG = 1f 8b 08 04,
+ *                        its extra field has a subfield 'B' 'C' of SLEN 2 (BSIZE), and with size = BSIZE + 1, data_off = 12 + XLEN,
+ *                        data_len = size - XLEN - 20 >= 0 and ISIZE <= 65536.  It stops at the first member that does not lie wholly
+ *                        inside len: *consumed = its offset, KQ_OK (feed a file piecewise).  A member that is not BGZF:
+ *                        KQ_ERR_INVALID, *consumed = its offset, *n_blocks = the blocks before it (a plain .gz shows on the first
+ *                        member).  More than cap blocks: KQ_ERR_CAPACITY, *n_blocks = the number needed.  Every read is checked
+ *                        against len.
+ *   kq_inflate_bgzf_dev  d_comp (device, comp_len bytes, any alignment) holds the members of `blocks` (a HOST array, `off` relative
+ *                        to d_comp).  d_text receives the concatenation of their texts; *n_text = the sum of ISIZE.  Synchronises.
+ *                        KQ_ERR_CAPACITY (with *n_text set) when cap is too small; d_text may be NULL to get *n_text only.
+ *                        KQ_ERR_INVALID for a list that does not lie inside comp_len, and for a member that fails (invalid DEFLATE
+ *                        data, a size other than ISIZE, a CRC-32 mismatch): the message names the FIRST failing member's index
+ *                        and the reason.  A failing member writes nothing; bytes at and behind *n_text are never written.
+ *                        n_blocks == 0: KQ_OK, *n_text = 0.
+ *   kq_count_bgzf_dev    a STREAM on the handle: consecutive calls carry the pieces of one file, in file order.  The first call
+ *                        begins at a record start.  Each call inflates its members behind the carry the previous call left on
+ *                        the device, finds the end of the last whole record (FASTQ: the byte after the last '\n' whose ordinal
+ *                        from the start of the text is a multiple of 4; FASTA: the last '>' that starts a line, if it is not the
+ *                        text's first byte), counts the text in front of it exactly as kq_count_fastx_dev counts that text, and
+ *                        keeps the rest as the new carry.  With KQ_BGZF_END the whole remaining text is counted (a final '\n'
+ *                        is optional) and the stream is empty again; kq_clear empties it too.  n_blocks == 0 is allowed.  Two
+ *                        small read-backs per call, each of which waits for the stream: the status record (failed member, cut),
+ *                        then the parser's batch size.
+ * The three device entries share staging buffers of the handle: one caller at a time per handle, like every entry point that
+ * works on the handle's stream.  (Compressed bytes in page-locked HOST memory have no entry of their own yet: copy them with
+ * kq_copy_async into a kq_dev_alloc block and call kq_count_bgzf_dev.)
+ * A corrupt member, or text the parser refuses, is not counted: every kq_sync up to the next kq_clear returns KQ_ERR_INVALID (for
+ * a corrupt member with its index in the call and the reason); a corrupt member also drops the carry.  Null pointers, an unknown
+ * format or flag, a block list outside comp_len: KQ_ERR_INVALID before any device work. */
+typedef struct { uint64_t off; uint32_t size; uint32_t data_off; uint32_t data_len; uint32_t crc32; uint32_t isize; } kq_bgzf_block;
+enum { KQ_BGZF_END = 1 };
+int  kq_bgzf_scan(const void* data, uint64_t len, kq_bgzf_block* blocks, uint64_t cap, uint64_t* n_blocks, uint64_t* consumed);
+int  kq_inflate_bgzf_dev(kq_handle* h, const void* d_comp, uint64_t comp_len, const kq_bgzf_block* blocks, uint64_t n_blocks,
+                         char* d_text, uint64_t cap, uint64_t* n_text);
+int  kq_count_bgzf_dev(kq_handle* h, const void* d_comp, uint64_t comp_len, const kq_bgzf_block* blocks, uint64_t n_blocks, int format, uint32_t flags);
+
 /* Hot loop 1 only (DBG::hashSequences :75-113): the (key, edge byte) records of a batch in
  * sequence order; edge byte layout = edgeBit (include/kreeq.h:6-18).  *n_out = number of records
  * (also set on KQ_ERR_CAPACITY).  keys/edges may be NULL to just count. */

@@ -17,12 +17,14 @@ ERR_CAPACITY = -6                        # KQ_ERR_CAPACITY
 # every symbol include/kreeq_amd.h declares
 SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profile", "kq_set_stream", "kq_get_stream", "kq_sync", "kq_flush", "kq_get_info", "kq_last_error",
            "kq_abi_version", "kq_device_available", "kq_device_memory", "kq_count_batch", "kq_count_batch_dev", "kq_host_alloc", "kq_host_free", "kq_count_batch_async", "kq_host_wait", "kq_pack_bases", "kq_count_packed_dev", "kq_count_packed_async",
-           "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_emit_records",
+           "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_bgzf_scan", "kq_inflate_bgzf_dev", "kq_count_bgzf_dev", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
            "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_dev_alloc", "kq_dev_free", "kq_copy_async", "kq_per_base_triples_dev", "kq_format_table_dev", "kq_format_table", "kq_lookup_keys", "kq_branch_scan", "kq_search_variants", "kq_merge", "kq_import", "kq_export",
            "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_best_first", "kq_subgraph_trim"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
+BGZF_END = 1                             # KQ_BGZF_END
+BGZF_BLOCK_DTYPE = np.dtype([("off", "<u8"), ("size", "<u4"), ("data_off", "<u4"), ("data_len", "<u4"), ("crc32", "<u4"), ("isize", "<u4"), ("pad", "<u4")])      # kq_bgzf_block
 TABLE_KWIG, TABLE_BED, TABLE_CSV = 1, 2, 3      # KQ_TABLE_*
 TABLE_SEG_HEADER = 1                     # KQ_TABLE_SEG_HEADER
 TABLE_SEG_DTYPE = np.dtype([("first", "<u8"), ("n", "<u8"), ("abs_pos", "<u8"), ("name_off", "<u4"), ("name_len", "<u4"), ("n_ctx", "<u4"), ("flags", "<u4")])      # kq_table_seg
@@ -117,6 +119,9 @@ def load():
     L.kq_parse_fastx_dev.argtypes = [vp, vp, u64, ci, vp, u64, C.POINTER(u64)]
     L.kq_count_fastx_dev.argtypes = [vp, vp, u64, ci]
     L.kq_count_fastx_async.argtypes = [vp, vp, u64, ci, C.POINTER(u64)]
+    L.kq_bgzf_scan.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.kq_inflate_bgzf_dev.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]
+    L.kq_count_bgzf_dev.argtypes = [vp, vp, u64, vp, u64, ci, u32]
     L.kq_emit_records.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.kq_emit_partitioned_dev.argtypes = [vp, vp, u64, ci, vp, vp, u64, vp]
     L.kq_emit_packed_dev.argtypes = [vp, vp, u64, ci, vp, u64, vp]
@@ -172,6 +177,23 @@ def pack_bases(bases: bytes):
     codes, inv = np.zeros(max(units, 1), dtype=np.uint32), np.zeros(max(units, 1), dtype=np.uint16)
     load().kq_pack_bases(_p(buf) if len(buf) else None, len(buf), _p(codes), _p(inv))
     return codes[:units], inv[:units]
+
+
+def bgzf_scan(data: bytes, cap=None):
+    """the BGZF members that lie wholly inside data (kq_bgzf_scan; host only) -> (blocks as BGZF_BLOCK_DTYPE, consumed bytes).
+    Raises KqError -1 for a member that is not BGZF (KqError.consumed = its offset, KqError.n_blocks = the blocks before it) and
+    -6 when cap is given and too small (KqError.n_blocks = the number needed)"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    n, used = C.c_uint64(0), C.c_uint64(0)
+    L = load()
+    room = len(buf) // 26 + 1 if cap is None else cap          # no member is shorter than 26 bytes
+    blocks = np.zeros(max(room, 1), dtype=BGZF_BLOCK_DTYPE)
+    rc = L.kq_bgzf_scan(_p(buf) if len(buf) else None, len(buf), _p(blocks) if room else None, room, C.byref(n), C.byref(used))
+    if rc != 0:
+        e = KqError(rc, L.kq_last_error().decode(errors="replace"))
+        e.n_blocks, e.consumed = n.value, used.value
+        raise e
+    return blocks[:n.value], used.value
 
 
 def device_available():
@@ -287,6 +309,26 @@ class KreeqDB:
         t = C.c_uint64(0)
         _check(load().kq_count_fastx_async(self._h, C.c_void_p(host_ptr), n, fmt, C.byref(t)))
         return t.value
+
+    def inflate_bgzf_dev(self, comp_ptr, comp_len, blocks, out_ptr, cap):
+        """BGZF members in device memory (blocks: BGZF_BLOCK_DTYPE, offsets relative to comp_ptr) -> their text at out_ptr (room
+        for cap bytes); returns its size.  out_ptr None / 0: the size only.  Raises KqError -6 when cap is too small
+        (KqError.needed holds the size), -1 for a bad list or a corrupt member (the message names the first one)"""
+        blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
+        nt = C.c_uint64(0)
+        rc = load().kq_inflate_bgzf_dev(self._h, C.c_void_p(comp_ptr), comp_len, _p(blocks) if len(blocks) else None, len(blocks),
+                                        C.c_void_p(out_ptr) if out_ptr else None, cap, C.byref(nt))
+        if rc != 0:
+            e = KqError(rc, load().kq_last_error().decode(errors="replace"))
+            e.needed = nt.value
+            raise e
+        return nt.value
+
+    def count_bgzf_dev(self, comp_ptr, comp_len, blocks, fmt, flags=0):
+        """one piece of a BGZF stream from device memory: inflate behind the carry, count the whole records, keep the rest;
+        flags = BGZF_END on the last piece"""
+        blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
+        _check(load().kq_count_bgzf_dev(self._h, C.c_void_p(comp_ptr), comp_len, _p(blocks) if len(blocks) else None, len(blocks), fmt, flags))
 
     def host_wait(self, ticket):
         _check(load().kq_host_wait(self._h, ticket))

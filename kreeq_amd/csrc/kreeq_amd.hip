@@ -25,11 +25,13 @@
 #include "kq_roff_host.h"
 #include "kq_seg_gate_host.h"
 #include "kq_select_host.h"
+#include "kq_bgzf_host.h"
 
 using namespace kq;
 
 #include "kq_kernels.h"
 #include "kq_fastx.h"
+#include "kq_bgzf.h"
 #include "kq_dbimage.h"
 #include "kq_subgraph.h"
 #include "kq_variants.h"
@@ -225,6 +227,13 @@ struct kq_handle {
     DevMem fx_res;                       // FxResult
     PinnedMem fx_res_host;               // its pinned mirror
     int fx_bad = 0;                      // a counted text broke its format: reported by kq_sync until kq_clear
+    // BGZF members on the device (kq_bgzf.h): the members' descriptors and their page-locked staging, the status record and its
+    // mirror, the text of one call (carry + the call's members) and the carry of a kq_count_bgzf_dev stream between calls
+    DevMem bz_desc, bz_stat, bz_text, bz_carry;
+    PinnedMem bz_desc_host, bz_stat_host;
+    uint64_t bz_carry_len = 0;
+    bool bz_bad = false;                 // a counted BGZF member was corrupt: reported by kq_sync until kq_clear
+    std::string bz_err;                  // its message
     bool hist_cache_off = false;         // the batch being counted lives in a library-owned buffer, which keeps its address and
                                          // changes its content: the address-keyed KQ_OPT_COUNT_MAP_PASSES cache must not see it
     bool test_fail_plan = false;         // KQ_OPT_TEST_FAIL_PLAN: the next partition plan fails with KQ_ERR_NOMEM (failure-path tests)
@@ -578,6 +587,7 @@ int kq_clear(kq_handle* h) {
     h->table_empty = true;
     h->n_pend = 0; h->arena_used = 0; h->pend_records = 0;      // records not applied yet are dropped with the rest
     h->fx_bad = 0;
+    h->bz_bad = false; h->bz_carry_len = 0;      // an open kq_count_bgzf_dev stream is dropped
     return KQ_OK;
 }
 
@@ -670,6 +680,7 @@ int kq_sync(kq_handle* h) {
     HIPC(hipSetDevice(h->device));
     HIPC(hipStreamSynchronize(h->stream));
     const int rc = check_errors(h);
+    if (h->bz_bad) return fail(KQ_ERR_INVALID, "%s: submitted for counting and skipped (kq_clear resets this)", h->bz_err.c_str());
     if (h->fx_bad) return fail(KQ_ERR_INVALID, "malformed %s text was submitted for counting and skipped (kq_clear resets this)", h->fx_bad == KQ_FASTX_FASTQ ? "FASTQ" : "FASTA");
     return rc;
 }
@@ -1486,6 +1497,162 @@ int kq_count_fastx_async(kq_handle* h, const char* text, uint64_t len, int forma
     }
     HIPC(hipEventRecord(h->in_consumed[s].get(), h->stream));
     return rc;
+}
+
+// ---- BGZF members on the device (kq_bgzf.h, kq_bgzf_host.h, kq_inflate_core.h) --------------------------------------------
+
+static_assert(sizeof(kq_bgzf_block) == sizeof(kqbgzf::Block) && offsetof(kq_bgzf_block, isize) == offsetof(kqbgzf::Block, isize), "kq_bgzf_block is kqbgzf::Block");
+
+int kq_bgzf_scan(const void* data, uint64_t len, kq_bgzf_block* blocks, uint64_t cap, uint64_t* n_blocks, uint64_t* consumed) {
+    if ((!data && len) || (!blocks && cap) || !n_blocks || !consumed) return fail(KQ_ERR_INVALID, "null argument");
+    const int rc = kqbgzf::scan(data, len, reinterpret_cast<kqbgzf::Block*>(blocks), cap, n_blocks, consumed);
+    if (rc == KQ_ERR_INVALID) return fail(rc, "the gzip member at byte %llu is not a BGZF block", (unsigned long long)*consumed);
+    if (rc == KQ_ERR_CAPACITY) return fail(rc, "block array too small: %llu blocks, room for %llu", (unsigned long long)*n_blocks, (unsigned long long)cap);
+    return rc;
+}
+
+// the list lies inside comp_len and every size is one a member can have -> *n_text = the sum of ISIZE
+static int bz_check(const kq_bgzf_block* blocks, uint64_t n_blocks, uint64_t comp_len, uint64_t* n_text) {
+    if (n_blocks >= (1ull << 31)) return fail(KQ_ERR_INVALID, "2^31 BGZF blocks or more in one call");
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n_blocks; ++i) {
+        const kq_bgzf_block& b = blocks[i];
+        const bool inside = b.off <= comp_len && b.size <= comp_len - b.off;
+        const bool shaped = b.size <= 65536 && (uint64_t)b.data_off + b.data_len + 8 <= b.size && b.isize <= kqbgzf::MAX_ISIZE;
+        if (!inside || !shaped)
+            return fail(KQ_ERR_INVALID, "BGZF block %llu (offset %llu, %u bytes) %s", (unsigned long long)i, (unsigned long long)b.off, b.size,
+                        inside ? "has impossible sizes" : "does not lie inside the compressed buffer");
+        total += b.isize;
+    }
+    *n_text = total;
+    return KQ_OK;
+}
+static int bz_prepare(kq_handle* h, uint64_t n_blocks) {
+    if (!h->bz_stat) HIPC(h->bz_stat.alloc(sizeof(BzStatus)));
+    if (!h->bz_stat_host) HIPC(h->bz_stat_host.alloc(sizeof(BzStatus)));
+    HIPC(h->bz_desc.ensure((size_t)n_blocks * sizeof(BzBlock)));
+    HIPC(h->bz_desc_host.ensure((size_t)n_blocks * sizeof(BzBlock)));
+    return KQ_OK;
+}
+// status record: no bad block, no newline, no cut
+static int bz_reset_status(kq_handle* h, hipStream_t st) {
+    HIPC(hipMemsetAsync(h->bz_stat.get(), 0xFF, sizeof(unsigned long long), st));
+    HIPC(hipMemsetAsync(h->bz_stat.as<char>() + sizeof(unsigned long long), 0, sizeof(BzStatus) - sizeof(unsigned long long), st));
+    return KQ_OK;
+}
+// inflate the members into d_text + base, on `st` (which the host has synchronised with since the previous use of the staging).
+// The descriptor staging and the status record belong to the handle: like every entry point that works on the handle's stream,
+// the BGZF entries take one caller at a time
+static int bz_launch(kq_handle* h, hipStream_t st, const void* d_comp, const kq_bgzf_block* blocks, uint64_t n_blocks, char* d_text, uint64_t base) {
+    BzBlock* desc = h->bz_desc_host.as<BzBlock>();
+    uint64_t out = base;
+    for (uint64_t i = 0; i < n_blocks; ++i) {
+        BzBlock d;
+        d.in_off = blocks[i].off + blocks[i].data_off; d.out_off = out; d.data_len = blocks[i].data_len; d.crc = blocks[i].crc32; d.isize = blocks[i].isize; d.pad = 0;
+        desc[i] = d;
+        out += blocks[i].isize;
+    }
+    HIPC(hipMemcpyAsync(h->bz_desc.get(), desc, (size_t)n_blocks * sizeof(BzBlock), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)n_blocks), dim3(64), 0, st, (const uint8_t*)d_comp, h->bz_desc.as<const BzBlock>(), (uint32_t)n_blocks,
+                       (uint8_t*)d_text, h->bz_stat.as<BzStatus>());
+    HIPC(hipGetLastError());
+    return KQ_OK;
+}
+static int bz_read_status(kq_handle* h, hipStream_t st) {
+    HIPC(hipMemcpyAsync(h->bz_stat_host.get(), h->bz_stat.get(), sizeof(BzStatus), hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    return KQ_OK;
+}
+static std::string bz_describe(const BzStatus* s) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "BGZF block %llu is corrupt (%s)", s->first_bad >> 8, kqinf::err_name((int)(s->first_bad & 0xFF)));
+    return buf;
+}
+
+int kq_inflate_bgzf_dev(kq_handle* h, const void* d_comp, uint64_t comp_len, const kq_bgzf_block* blocks, uint64_t n_blocks, char* d_text, uint64_t cap,
+                        uint64_t* n_text) {
+    if (!h || !n_text || ((!d_comp || !blocks) && n_blocks)) return fail(KQ_ERR_INVALID, "null argument");
+    *n_text = 0;
+    if (!n_blocks) return KQ_OK;
+    uint64_t total = 0;
+    int rc = bz_check(blocks, n_blocks, comp_len, &total); if (rc) return rc;
+    *n_text = total;
+    if (!d_text) return KQ_OK;
+    if (total > cap) return fail(KQ_ERR_CAPACITY, "output buffer too small: %llu bytes of text, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    HIPC(hipSetDevice(h->device));
+    rc = bz_prepare(h, n_blocks); if (rc) return rc;
+    rc = bz_reset_status(h, h->stream); if (rc) return rc;
+    rc = bz_launch(h, h->stream, d_comp, blocks, n_blocks, d_text, 0); if (rc) return rc;
+    rc = bz_read_status(h, h->stream); if (rc) return rc;
+    const BzStatus* s = h->bz_stat_host.as<BzStatus>();
+    if (s->first_bad != ~0ull) return fail(KQ_ERR_INVALID, "%s", bz_describe(s).c_str());
+    return KQ_OK;
+}
+
+static int bz_args(kq_handle* h, const void* comp, const kq_bgzf_block* blocks, uint64_t n_blocks, int format, uint32_t flags) {
+    if (!h || ((!comp || !blocks) && n_blocks)) return fail(KQ_ERR_INVALID, "null argument");
+    if (format != KQ_FASTX_FASTQ && format != KQ_FASTX_FASTA) return fail(KQ_ERR_INVALID, "format must be KQ_FASTX_FASTQ or KQ_FASTX_FASTA, not %d", format);
+    if (flags & ~(uint32_t)KQ_BGZF_END) return fail(KQ_ERR_INVALID, "unknown flag bits %#x", flags);
+    return KQ_OK;
+}
+// One step of a BGZF stream, on the handle's stream: carry + the members' text -> cut -> parse [0, cut) into fx_out -> count it;
+// [cut, end) is the next carry.  Two small read-backs: the status record (bad member, cut), then the parser's batch size.
+static int bz_count_step(kq_handle* h, const void* d_comp, const kq_bgzf_block* blocks, uint64_t n_blocks, uint64_t n_new, int format, uint32_t flags) {
+    const hipStream_t st = h->stream;
+    DevMem& parsed = h->fx_out;
+    const uint64_t carry = h->bz_carry_len, total = carry + n_new;
+    const bool end = (flags & KQ_BGZF_END) != 0;
+    if (!total) return KQ_OK;
+    int rc = bz_prepare(h, n_blocks); if (rc) return rc;
+    if (h->bz_text.bytes() < total + 64) {
+        HIPC(hipStreamSynchronize(st));                    // (nothing may still read the old buffer)
+        HIPC(h->bz_text.ensure(total + 64));
+    }
+    char* text = h->bz_text.as<char>();
+    if (carry) HIPC(hipMemcpyAsync(text, h->bz_carry.get(), carry, hipMemcpyDeviceToDevice, st));
+    rc = bz_reset_status(h, st); if (rc) return rc;
+    if (n_blocks) { rc = bz_launch(h, st, d_comp, blocks, n_blocks, text, carry); if (rc) return rc; }
+    if (!end) {
+        if (format == KQ_FASTX_FASTQ) {
+            hipLaunchKernelGGL(k_bgzf_count_nl, dim3(grid_for(h, (total + 15) / 16, 256)), dim3(256), 0, st, (const uint8_t*)text, total, h->bz_stat.as<BzStatus>());
+            hipLaunchKernelGGL((k_bgzf_cut<FX_FASTQ>), dim3(1), dim3(BZ_CUT_THREADS), 0, st, (const uint8_t*)text, total, h->bz_stat.as<BzStatus>());
+        } else hipLaunchKernelGGL((k_bgzf_cut<FX_FASTA>), dim3(1), dim3(BZ_CUT_THREADS), 0, st, (const uint8_t*)text, total, h->bz_stat.as<BzStatus>());
+        HIPC(hipGetLastError());
+    }
+    rc = bz_read_status(h, st); if (rc) return rc;
+    const BzStatus* s = h->bz_stat_host.as<BzStatus>();
+    if (s->first_bad != ~0ull) {
+        // not counted, and the stream ends here: kq_sync reports it up to kq_clear
+        h->bz_bad = true; h->bz_err = bz_describe(s); h->bz_carry_len = 0;
+        return KQ_OK;
+    }
+    const uint64_t cut = end ? total : std::min<uint64_t>(s->cut, total);
+    h->bz_carry_len = total - cut;
+    if (total > cut) {
+        // the carry was copied into the text above and `st` has been synchronised since: its buffer may be replaced
+        HIPC(h->bz_carry.ensure(total - cut));
+        HIPC(hipMemcpyAsync(h->bz_carry.get(), text + cut, total - cut, hipMemcpyDeviceToDevice, st));
+    }
+    if (!cut) { HIPC(hipStreamSynchronize(st)); return KQ_OK; }
+    rc = fx_prepare(h, fx_units_of(text, cut)); if (rc) return rc;
+    if (parsed.bytes() < cut + 64) {
+        if (parsed) HIPC(hipStreamSynchronize(st));        // (an earlier count may still read the old buffer)
+        HIPC(parsed.ensure(cut + 64));
+    }
+    fx_scan(h, st, text, cut, format);
+    fx_apply(h, st, text, cut, format, parsed.as<char>());
+    rc = fx_read_result(h, st); if (rc) return rc;             // (the carry has been copied by now, too)
+    if (h->fx_host()->bad) { h->fx_bad = format; return KQ_OK; }       // not counted; kq_sync reports it
+    HistCacheOff guard(h);
+    return count_seq_dev(h, parsed.as<const char>(), nullptr, h->fx_host()->n_bases);
+}
+
+int kq_count_bgzf_dev(kq_handle* h, const void* d_comp, uint64_t comp_len, const kq_bgzf_block* blocks, uint64_t n_blocks, int format, uint32_t flags) {
+    int rc = bz_args(h, d_comp, blocks, n_blocks, format, flags); if (rc) return rc;
+    uint64_t n_new = 0;
+    rc = bz_check(blocks, n_blocks, comp_len, &n_new); if (rc) return rc;
+    HIPC(hipSetDevice(h->device));
+    return bz_count_step(h, d_comp, blocks, n_blocks, n_new, format, flags);
 }
 
 static int emit_ordered(kq_handle* h, const char* d_bases, uint64_t len, uint64_t* d_keys, uint8_t* d_edges, uint64_t cap,
