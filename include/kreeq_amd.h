@@ -407,6 +407,18 @@ int   kq_copy_async(kq_handle* h, void* dst, const void* src, uint64_t bytes, in
 int  kq_per_base_triples_dev(kq_handle* h, const kq_dbgbase* d_per_base, const uint64_t* seg_start, const uint64_t* seg_len,
                              uint64_t n_segs, uint32_t* d_triples);
 
+/* The same payload accumulated over map-range passes.  The lists mean what they mean above (position g of the output is
+ * entry seg_start[s] + g - (positions of the segments before s)), and per listed position: an entry with any of its 16 bytes
+ * non-zero is STORED -- its oriented triple is written to d_triples[3g .. 3g + 2] and the entry is set to 16 zero bytes; an
+ * all-zero entry leaves its triple untouched.  Nothing between the segments is read or written.  Afterwards d_per_base is
+ * zero over the listed segments again, so the same array serves the next lookup (the next group of sequences or the next
+ * map range) without a memset, and because a position is evaluated in exactly one map range and a lookup stores only found
+ * k-mers, d_triples (zeroed once) holds after all ranges what kq_per_base_triples_dev gives after one whole-range lookup.
+ * Asynchronous like kq_per_base_triples_dev; KQ_ERR_INVALID also for segments that are not ascending and non-overlapping
+ * (seg_start[s] >= seg_start[s - 1] + seg_len[s - 1]; checked on the host before any device work). */
+int  kq_per_base_merge_dev(kq_handle* h, kq_dbgbase* d_per_base, const uint64_t* seg_start, const uint64_t* seg_len,
+                           uint64_t n_segs, uint32_t* d_triples);
+
 /* Triples -> decimal text, formatted on the device.  A call formats PIECES in order; piece p covers the triples
  * first .. first + n - 1 and the coordinates abs_pos .. abs_pos + n - 1, and names + name_off / name_len is its sequence name.
  *   KQ_TABLE_KWIG  per piece: when flags has KQ_TABLE_SEG_HEADER the line "fixedStep chrom=<name> start=<abs_pos> step=1\n",

@@ -19,7 +19,7 @@ SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profi
            "kq_abi_version", "kq_device_available", "kq_device_memory", "kq_count_batch", "kq_count_batch_dev", "kq_host_alloc", "kq_host_free", "kq_count_batch_async", "kq_host_wait", "kq_pack_bases", "kq_count_packed_dev", "kq_count_packed_async",
            "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_bgzf_scan", "kq_inflate_bgzf_dev", "kq_count_bgzf_dev", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
-           "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_dev_alloc", "kq_dev_free", "kq_copy_async", "kq_per_base_triples_dev", "kq_format_table_dev", "kq_format_table", "kq_lookup_keys", "kq_branch_scan", "kq_search_variants", "kq_merge", "kq_import", "kq_export",
+           "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_dev_alloc", "kq_dev_free", "kq_copy_async", "kq_per_base_triples_dev", "kq_per_base_merge_dev", "kq_format_table_dev", "kq_format_table", "kq_lookup_keys", "kq_branch_scan", "kq_search_variants", "kq_merge", "kq_import", "kq_export",
            "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_best_first", "kq_subgraph_trim"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
@@ -142,6 +142,7 @@ def load():
     L.kq_dev_free.restype = None
     L.kq_copy_async.argtypes = [vp, vp, vp, u64, ci]
     L.kq_per_base_triples_dev.argtypes = [vp, vp, vp, vp, u64, vp]
+    L.kq_per_base_merge_dev.argtypes = [vp, vp, vp, vp, u64, vp]
     L.kq_format_table_dev.argtypes = [vp, ci, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]
     L.kq_format_table.argtypes = [vp, ci, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]
     L.kq_lookup_keys.argtypes = [vp, vp, u64, vp]
@@ -426,6 +427,13 @@ class KreeqDB:
         start = np.array([s for s, _ in segments], dtype=np.uint64)
         length = np.array([n for _, n in segments], dtype=np.uint64)
         _check(load().kq_per_base_triples_dev(self._h, C.c_void_p(per_base_ptr), _p(start), _p(length), len(segments), C.c_void_p(triples_ptr)))
+
+    def per_base_merge_dev(self, per_base_ptr, segments, triples_ptr):
+        """one map-range pass folded into the accumulated triples at triples_ptr: the stored (non-zero) entries of the listed
+        segments overwrite their triples and are zeroed, zero entries leave theirs alone; asynchronous on the handle's stream"""
+        start = np.array([s for s, _ in segments], dtype=np.uint64)
+        length = np.array([n for _, n in segments], dtype=np.uint64)
+        _check(load().kq_per_base_merge_dev(self._h, C.c_void_p(per_base_ptr), _p(start), _p(length), len(segments), C.c_void_p(triples_ptr)))
 
     def format_table_raw(self, fmt, triples, n_triples, segs, n_segs, names, names_len, out, cap, n_out=True, dev=False):
         """kq_format_table(_dev) as it is; every pointer a ctypes pointer / address or None -> (return code, *n_out)"""

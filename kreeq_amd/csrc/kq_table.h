@@ -211,4 +211,24 @@ __global__ __launch_bounds__(256) void k_tab_triples(const kq_dbgbase* __restric
     }
 }
 
+// ---- per-base entries of one map-range pass -> the accumulated triples (kq_per_base_merge_dev) ---------------------------
+// The lists are k_tab_triples'.  A position is evaluated in exactly one pass and k_lookup stores only found k-mers, so the
+// passes' stored entries are disjoint: a stored entry (any of its 16 bytes set) overwrites its triple and is zeroed, a zero
+// entry leaves the triple of an earlier pass alone, and per_base is all zero over the segments again when the kernel ends.
+// One position per thread: a 16-byte load, and for a stored entry three dword stores and a 16-byte store.  per_base is read
+// and written, hence neither const nor __restrict__; no entry and no triple belongs to two threads.
+__global__ __launch_bounds__(256) void k_tab_merge(kq_dbgbase* per_base, const unsigned long long* __restrict__ seg_start,
+                                                    const unsigned long long* __restrict__ out_start, uint32_t n_segs, uint64_t n, uint32_t* triples) {
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t lo = 0, hi = n_segs;
+        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (out_start[mid] <= g) lo = mid; else hi = mid; }
+        uint4* const p = (uint4*)(per_base + seg_start[lo] + (g - out_start[lo]));
+        const uint4 e = *p;                                                                   // fw, bw, cov, isFw | pad
+        if ((e.x | e.y | e.z | e.w) == 0) continue;
+        const bool fw = (e.w & 0xFFu) != 0;
+        triples[g * 3] = e.z; triples[g * 3 + 1] = fw ? e.x : e.y; triples[g * 3 + 2] = fw ? e.y : e.x;
+        *p = make_uint4(0, 0, 0, 0);
+    }
+}
+
 }  // namespace kq

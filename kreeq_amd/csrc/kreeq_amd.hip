@@ -2082,6 +2082,31 @@ int kq_per_base_triples_dev(kq_handle* h, const kq_dbgbase* d_per_base, const ui
     return KQ_OK;
 }
 
+int kq_per_base_merge_dev(kq_handle* h, kq_dbgbase* d_per_base, const uint64_t* seg_start, const uint64_t* seg_len, uint64_t n_segs, uint32_t* d_triples) {
+    if (!h || ((!seg_start || !seg_len) && n_segs)) return fail(KQ_ERR_INVALID, "null argument");
+    if (n_segs >= 0xFFFFFFFFull) return fail(KQ_ERR_INVALID, "%llu segments: fewer than 2^32 - 1 per call", (unsigned long long)n_segs);
+    std::vector<unsigned long long> lists(2 * (size_t)n_segs + 1);          // seg_start[n_segs], out_start[n_segs + 1]
+    unsigned long long total = 0, end = 0;                                  // end: behind the entries of the segments so far
+    for (uint64_t s = 0; s < n_segs; ++s) {
+        if (seg_start[s] < end || seg_len[s] > ~0ull - seg_start[s])         // (two threads would consume one entry)
+            return fail(KQ_ERR_INVALID, "segment %llu (%llu + %llu) is not behind the one before it", (unsigned long long)s, (unsigned long long)seg_start[s], (unsigned long long)seg_len[s]);
+        end = seg_start[s] + seg_len[s];
+        lists[s] = seg_start[s]; lists[n_segs + s] = total; total += seg_len[s];
+    }
+    lists[2 * n_segs] = total;
+    if (!total) return KQ_OK;
+    if (!d_per_base || !d_triples) return fail(KQ_ERR_INVALID, "null argument");
+    HIPC(hipSetDevice(h->device));
+    HIPC(h->tab_segs.ensure(lists.size() * 8));                          // (frees the previous lists only after the device has finished with them)
+    unsigned long long* d_lists = h->tab_segs.as<unsigned long long>();
+    HIPC(hipMemcpyAsync(d_lists, lists.data(), lists.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIPC(hipStreamSynchronize(h->stream));                                // `lists` is pageable and leaves scope
+    hipLaunchKernelGGL(k_tab_merge, dim3(grid_for(h, total, 256)), dim3(256), 0, h->stream, d_per_base, (const unsigned long long*)d_lists,
+                       (const unsigned long long*)(d_lists + n_segs), (uint32_t)n_segs, (uint64_t)total, d_triples);
+    HIPC(hipGetLastError());
+    return KQ_OK;
+}
+
 // the checks of kq_format_table*, and the lines before every piece
 static int tab_check(kq_handle* h, int format, const void* triples, uint64_t n_triples, const kq_table_seg* segs, uint64_t n_segs, const char* names, uint64_t names_len,
                      uint64_t* n_out, std::vector<unsigned long long>* line_start) {

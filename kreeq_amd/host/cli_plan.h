@@ -96,6 +96,43 @@ inline SegmentLists all_segments(const std::vector<SeqRecord>& seqs) {
 struct Triple { uint32_t cov, fw, bw; };                        // one position of a per-base table, as the .bkwig payload holds it
 inline Triple oriented(const kq_dbgbase& b) { return {b.cov, b.isFw ? b.fw : b.bw, b.isFw ? b.bw : b.fw}; }
 
+// The per-base table of a run in map ranges, accumulated on the device: the triples of the whole genome lie in one array,
+// segment after segment, and every range looks the sequences up group by group (next_call) into one text buffer and one
+// per-base array sized for the largest group.  A group's segment lists are rebased to its text (kq_per_base_merge_dev takes
+// them as they are), and its triples begin at first_triple of the accumulator.
+struct TableGroup {
+    size_t lo = 0, hi = 0;                                      // its sequences
+    uint64_t text_off = 0, text_len = 0;                        // its range of the joined text (join_sequences over all sequences)
+    std::vector<uint64_t> seg_start, seg_len;                   // seg_start: inside the group's text
+    uint64_t first_triple = 0, n_triples = 0;
+};
+struct TablePassPlan {
+    std::vector<TableGroup> groups;
+    bool fits = true;                                           // false: a sequence (with its separator) exceeds the limit
+    uint64_t acc_bytes = 0, max_text = 0, max_per_base = 0;     // 12 x positions; the largest group's text and per-base array
+    uint64_t device_bytes() const { return acc_bytes + max_text + max_per_base; }
+};
+inline TablePassPlan plan_table_passes(const std::vector<SeqRecord>& seqs, const SegmentLists& segs, uint64_t limit) {
+    TablePassPlan p;
+    p.fits = all_fit(seqs, limit);
+    uint64_t text_off = 0, first = 0;
+    for (size_t lo = 0, hi; lo < seqs.size(); lo = hi) {
+        hi = next_call(seqs, lo, limit);
+        TableGroup g;
+        g.lo = lo; g.hi = hi; g.text_off = text_off; g.first_triple = first;
+        for (size_t s = lo; s < hi; ++s) {
+            for (auto& seg : segs[s]) { g.seg_start.push_back(g.text_len + seg.first); g.seg_len.push_back(seg.second); g.n_triples += seg.second; }
+            g.text_len += seqs[s].seq.size() + 1;
+        }
+        text_off += g.text_len; first += g.n_triples;
+        p.max_text = std::max(p.max_text, g.text_len);
+        p.max_per_base = std::max(p.max_per_base, g.text_len * (uint64_t)sizeof(kq_dbgbase));
+        p.groups.push_back(std::move(g));
+    }
+    p.acc_bytes = first * sizeof(Triple);
+    return p;
+}
+
 // The segments of sequences [lo, hi) -- one device call, whose triples lie segment after segment -- cut into chunks of at most
 // `chunk` lines for kq_format_table_dev: whole segments or parts of one.  The first piece of a segment carries the header
 // flag; a later piece of an expanded table (.bed / .csvtable) has up to k - 1 positions before it as its window's history.

@@ -1,5 +1,6 @@
 // The QV table and the per-base outputs of `kreeq validate` (reference src/kreeq.cpp:78-106, src/kreeq-output.cpp:138-399):
-// three host writers over the per-base vector, and the same four files from the device.
+// three host writers over the per-base vector, and the same four files from the device: from one lookup over a resident
+// table, or accumulated over map ranges.
 #include "per_base.h"
 
 #include <fcntl.h>
@@ -135,6 +136,62 @@ struct TableOut {
     }
 };
 
+// "Triples on the device -> file", the half that both device paths share: the file with its head (.kwig's k, .bkwig's index),
+// and per call -- sequences [lo, hi), whose triples lie segment after segment at d_triples -- the payload copied out as it is
+// (.bkwig) or formatted in chunks of at most KQ_TABLE_CHUNK_LINES positions (cut_table_chunks + kq_format_table_dev), through
+// the two page-locked buffers of TableOut.
+struct DeviceTableFile {
+    const Run& r;
+    kq_handle* h;
+    const SegmentLists& segs;
+    const int fmt;                                                   // 0: .bkwig
+    const uint64_t chunk = env_u64("KQ_TABLE_CHUNK_LINES", (uint64_t)1 << 20);
+    TableOut out;
+    std::string names;
+    std::vector<uint32_t> name_off;
+    char* d_text = nullptr;
+    uint64_t d_text_cap = 0;
+    double t_format = 0, t_copy = 0;
+    static int format_of(const std::string& ext) { return ext == "kwig" ? KQ_TABLE_KWIG : ext == "bed" ? KQ_TABLE_BED : ext == "csvtable" ? KQ_TABLE_CSV : 0; }
+    DeviceTableFile(const Run& run, const SegmentLists& sl) : r(run), h(run.h), segs(sl), fmt(format_of(run.plan.ext)) {
+        out.fd = ::open(r.ui.outFile.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        if (out.fd < 0) die("Error: cannot write " + r.ui.outFile + ": " + strerror(errno));
+        if (fmt == KQ_TABLE_KWIG) out.direct(std::to_string(r.k) + "\n");
+        if (fmt == 0) { std::ostringstream index; write_bkwig_index(index, r, segs); out.direct(index.str()); }
+        for (auto& s : r.seqs) { name_off.push_back((uint32_t)names.size()); names += s.header; }
+        name_off.push_back((uint32_t)names.size());
+    }
+    ~DeviceTableFile() { kq_dev_free(h, d_text); }
+    // a chunk that lies on the device -> the next page-locked buffer -> the file
+    void copy_out(const void* d_src, uint64_t bytes) {
+        char* dst = out.next(bytes);
+        const double t0 = now_s();
+        kq_or_die(kq_copy_async(h, dst, d_src, bytes, KQ_COPY_TO_HOST));
+        kq_or_die(kq_sync(h));
+        t_copy += now_s() - t0;
+        out.submit(bytes);
+    }
+    void write_call(size_t lo, size_t hi, const uint32_t* d_triples, uint64_t n_triples) {
+        if (fmt == 0) {                                              // .bkwig: the payload is the triples
+            for (uint64_t a = 0; a < n_triples; a += chunk) copy_out(d_triples + a * 3, std::min(chunk, n_triples - a) * 12);
+            return;
+        }
+        for (auto& pieces : cut_table_chunks(segs, lo, hi, name_off, chunk, r.k, fmt == KQ_TABLE_BED || fmt == KQ_TABLE_CSV)) {      // the text, chunk by chunk
+            uint64_t need = 0;
+            const double t0 = now_s();
+            kq_or_die(kq_format_table_dev(h, fmt, d_triples, n_triples, pieces.data(), pieces.size(), names.data(), names.size(), nullptr, 0, &need));
+            if (need > d_text_cap) {
+                kq_dev_free(h, d_text); d_text_cap = need + need / 8 + 4096; d_text = (char*)kq_dev_alloc(h, d_text_cap);
+                if (!d_text) die("Error: no device memory for " + std::to_string(d_text_cap) + " bytes of the per-base table");
+            }
+            kq_or_die(kq_format_table_dev(h, fmt, d_triples, n_triples, pieces.data(), pieces.size(), names.data(), names.size(), d_text, d_text_cap, &need));
+            t_format += now_s() - t0;
+            copy_out(d_text, need);
+        }
+    }
+    void finish() { out.wait(); }                                    // every chunk has reached the file
+};
+
 }  // namespace
 
 void print_qv(const Run& r) {
@@ -153,44 +210,21 @@ void print_qv(const Run& r) {
 bool table_device_wanted(const Run& r) { return env_flag("KQ_TABLE_DEVICE") && !r.ui.inSequence.empty() && all_fit(r.seqs, kDeviceCallBytes); }
 
 // Whole sequences are grouped into calls of at most kDeviceCallBytes of joined text.  Per call the lookup fills a per-base
-// array that stays on the device, kq_per_base_triples_dev makes the .bkwig payload of the call's segments from it, and that
-// payload is either copied out as it is (.bkwig) or formatted in chunks of at most KQ_TABLE_CHUNK_LINES positions
-// (kq_format_table_dev).  KQ_TABLE_TRACE=1 prints the wall clock of the steps to stderr.
+// array that stays on the device, kq_per_base_triples_dev makes the .bkwig payload of the call's segments from it, and
+// DeviceTableFile takes that payload to the file.  KQ_TABLE_TRACE=1 prints the wall clock of the steps to stderr.
 void write_per_base_device(Run& r) {
     verbose("per-base table written by the device formatter");
     verbose("Validating sequence");
     kq_handle* h = r.h;
-    const std::string& ext = r.plan.ext;
-    const int fmt = ext == "kwig" ? KQ_TABLE_KWIG : ext == "bed" ? KQ_TABLE_BED : ext == "csvtable" ? KQ_TABLE_CSV : 0;      // 0: .bkwig
     const SegmentLists segs = all_segments(r.seqs);
-    TableOut out;
-    out.fd = ::open(r.ui.outFile.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (out.fd < 0) die("Error: cannot write " + r.ui.outFile + ": " + strerror(errno));
-    if (fmt == KQ_TABLE_KWIG) out.direct(std::to_string(r.k) + "\n");
-    if (fmt == 0) { std::ostringstream index; write_bkwig_index(index, r, segs); out.direct(index.str()); }
-    std::string names;
-    std::vector<uint32_t> name_off;
-    for (auto& s : r.seqs) { name_off.push_back((uint32_t)names.size()); names += s.header; }
-    name_off.push_back((uint32_t)names.size());
-    const uint64_t chunk = env_u64("KQ_TABLE_CHUNK_LINES", (uint64_t)1 << 20);
-    double t_lookup = 0, t_format = 0, t_copy = 0;
-    char* d_text = nullptr;
-    uint64_t d_text_cap = 0;
+    DeviceTableFile file(r, segs);
+    double t_lookup = 0;
     auto dev_alloc = [&](uint64_t bytes) { void* p = kq_dev_alloc(h, bytes); if (!p) die("Error: no device memory for " + std::to_string(bytes) + " bytes of the per-base table"); return p; };
-    // a chunk that lies on the device -> the next page-locked buffer -> the file
-    auto copy_out = [&](const void* d_src, uint64_t bytes) {
-        char* dst = out.next(bytes);
-        const double t0 = now_s();
-        kq_or_die(kq_copy_async(h, dst, d_src, bytes, KQ_COPY_TO_HOST));
-        kq_or_die(kq_sync(h));
-        t_copy += now_s() - t0;
-        out.submit(bytes);
-    };
     for (size_t lo = 0, hi; lo < r.seqs.size(); lo = hi) {
         hi = next_call(r.seqs, lo, kDeviceCallBytes);
         const uint64_t len = (hi < r.seqs.size() ? r.genome.offset[hi] : r.genome.text.size()) - r.genome.offset[lo];
         // 1. lookup with the per-base array on the device, 2. the triples of the call's segments
-        double t0 = now_s();
+        const double t0 = now_s();
         std::vector<uint64_t> seg_start, seg_len;
         uint64_t n_triples = 0;
         for (size_t s = lo; s < hi; ++s)
@@ -208,25 +242,76 @@ void write_per_base_device(Run& r) {
         for (int i = 0; i < 3; ++i) r.counters[i] += ctr[i];
         kq_dev_free(h, d_bases); kq_dev_free(h, d_pb); kq_dev_free(h, d_ctr);
         t_lookup += now_s() - t0;
-        if (fmt == 0) {                                              // .bkwig: the payload is the triples
-            for (uint64_t a = 0; a < n_triples; a += chunk) copy_out(d_triples + a * 3, std::min(chunk, n_triples - a) * 12);
-        } else {                                                     // 3. the text, chunk by chunk
-            for (auto& pieces : cut_table_chunks(segs, lo, hi, name_off, chunk, r.k, fmt == KQ_TABLE_BED || fmt == KQ_TABLE_CSV)) {
-                uint64_t need = 0;
-                t0 = now_s();
-                kq_or_die(kq_format_table_dev(h, fmt, d_triples, n_triples, pieces.data(), pieces.size(), names.data(), names.size(), nullptr, 0, &need));
-                if (need > d_text_cap) { kq_dev_free(h, d_text); d_text_cap = need + need / 8 + 4096; d_text = (char*)dev_alloc(d_text_cap); }
-                kq_or_die(kq_format_table_dev(h, fmt, d_triples, n_triples, pieces.data(), pieces.size(), names.data(), names.size(), d_text, d_text_cap, &need));
-                t_format += now_s() - t0;
-                copy_out(d_text, need);
-            }
-        }
+        file.write_call(lo, hi, d_triples, n_triples);               // 3. the file
         kq_dev_free(h, d_triples);                                   // (every chunk of the call has left the device)
     }
-    out.wait();
-    kq_dev_free(h, d_text);
+    file.finish();
     print_qv(r);
-    if (env_flag("KQ_TABLE_TRACE")) fprintf(stderr, "[table] device: lookup %.3f s, format %.3f s, copy %.3f s, write %.3f s, %llu bytes\n", t_lookup, t_format, t_copy, out.t_write, (unsigned long long)out.bytes);
+    if (env_flag("KQ_TABLE_TRACE")) fprintf(stderr, "[table] device: lookup %.3f s, format %.3f s, copy %.3f s, write %.3f s, %llu bytes\n", t_lookup, file.t_format, file.t_copy, file.out.t_write, (unsigned long long)file.out.bytes);
+}
+
+// ---- the same under map-range passes: the triples accumulate on the device ------------------------------------------------
+bool table_passes_wanted(const Run& r) { return env_flag("KQ_TABLE_DEVICE") && env_flag("KQ_TABLE_DEVICE_PASSES") && !r.ui.inSequence.empty(); }
+
+static void table_passes_free(Run& r, TablePasses& t) {
+    kq_dev_free(r.h, t.d_acc); kq_dev_free(r.h, t.d_text); kq_dev_free(r.h, t.d_pb); kq_dev_free(r.h, t.d_ctr);
+    t.d_acc = nullptr; t.d_text = nullptr; t.d_pb = nullptr; t.d_ctr = nullptr;
+}
+
+bool table_passes_begin(Run& r, TablePasses& t) {
+    t.segs = all_segments(r.seqs);
+    t.plan = plan_table_passes(r.seqs, t.segs, env_u64("KQ_TABLE_CALL_BYTES", kDeviceCallBytes));
+    t.trace = env_flag("KQ_TABLE_TRACE");
+    const uint64_t bytes = t.plan.device_bytes();
+    auto fall_back = [&](const std::string& why) {
+        table_passes_free(r, t);
+        verbose("per-base table not accumulated on the device (" + std::to_string(bytes) + " bytes): " + why);
+        return false;
+    };
+    if (!t.plan.fits) return fall_back("a sequence exceeds the call limit");
+    if (bytes > env_u64("KQ_TABLE_ACC_MAX_BYTES", ~0ull)) return fall_back("more than KQ_TABLE_ACC_MAX_BYTES");
+    t.d_acc = (uint32_t*)kq_dev_alloc(r.h, t.plan.acc_bytes);        // (all four zero-filled)
+    t.d_text = (char*)kq_dev_alloc(r.h, t.plan.max_text);
+    t.d_pb = (kq_dbgbase*)kq_dev_alloc(r.h, t.plan.max_per_base);
+    t.d_ctr = (uint64_t*)kq_dev_alloc(r.h, 3 * sizeof(uint64_t));
+    if (!t.d_acc || !t.d_text || !t.d_pb || !t.d_ctr) return fall_back("no device memory");
+    return true;
+}
+
+void table_passes_range(Run& r, TablePasses& t, int lo, int hi) {
+    kq_handle* h = r.h;
+    for (const TableGroup& g : t.plan.groups) {
+        double t0 = now_s();
+        kq_or_die(kq_copy_async(h, t.d_text, r.genome.text.data() + g.text_off, g.text_len, KQ_COPY_TO_DEVICE));
+        kq_or_die(kq_lookup_sequence_dev(h, t.d_text, g.text_len, r.ui.covCutOff, (uint16_t)lo, (uint16_t)hi, t.d_pb, t.d_ctr));
+        if (t.trace) { kq_or_die(kq_sync(h)); t.t_lookup += now_s() - t0; t0 = now_s(); }      // (the steps are asynchronous: a trace waits to tell them apart)
+        kq_or_die(kq_per_base_merge_dev(h, t.d_pb, g.seg_start.data(), g.seg_len.data(), g.seg_start.size(), t.d_acc + 3 * g.first_triple));
+        if (t.trace) { kq_or_die(kq_sync(h)); t.t_merge += now_s() - t0; }
+    }
+    ++t.n_ranges;
+}
+
+void table_passes_write(Run& r, TablePasses& t) {
+    verbose("per-base table written by the device formatter");
+    verbose("per-base table accumulated on the device over " + std::to_string(t.n_ranges) + " map ranges in " + std::to_string(t.plan.groups.size()) + " calls");
+    kq_handle* h = r.h;
+    uint64_t ctr[3] = {0, 0, 0};
+    kq_or_die(kq_copy_async(h, ctr, t.d_ctr, sizeof ctr, KQ_COPY_TO_HOST));
+    kq_or_die(kq_sync(h));
+    for (int i = 0; i < 3; ++i) r.counters[i] += ctr[i];
+    kq_dev_free(h, t.d_text); kq_dev_free(h, t.d_pb); kq_dev_free(h, t.d_ctr);       // (room for the formatter's text)
+    t.d_text = nullptr; t.d_pb = nullptr; t.d_ctr = nullptr;
+    uint64_t bytes = 0;
+    double t_format = 0, t_copy = 0, t_write = 0;
+    {
+        DeviceTableFile file(r, t.segs);
+        for (const TableGroup& g : t.plan.groups) file.write_call(g.lo, g.hi, t.d_acc + 3 * g.first_triple, g.n_triples);
+        file.finish();
+        bytes = file.out.bytes; t_format = file.t_format; t_copy = file.t_copy; t_write = file.out.t_write;
+    }
+    table_passes_free(r, t);
+    if (t.trace) fprintf(stderr, "[table] device passes: lookup %.3f s, merge %.3f s, format %.3f s, copy %.3f s, write %.3f s, %llu bytes, %d map ranges, %llu calls\n",
+                         t.t_lookup, t.t_merge, t_format, t_copy, t_write, (unsigned long long)bytes, t.n_ranges, (unsigned long long)t.plan.groups.size());
 }
 
 void write_per_base_host(const Run& r) {

@@ -26,4 +26,27 @@ bool table_device_wanted(const Run& r);
 void write_per_base_device(Run& r);
 void write_per_base_host(const Run& r);
 
+// Device, under map-range passes (KQ_TABLE_DEVICE=1 and KQ_TABLE_DEVICE_PASSES=1, off by default): the oriented triples of the
+// whole genome accumulate in one device array over the ranges.  begin() plans (plan_table_passes, with KQ_TABLE_CALL_BYTES as
+// the group limit) and takes the accumulator, one text buffer, one per-base array and the counters BEFORE the first fill, so
+// that the count path sizes its arena around them; false -- a sequence above the limit, more than KQ_TABLE_ACC_MAX_BYTES, no
+// memory -- leaves nothing allocated, logs the bytes and the reason, and the host path runs.  range() follows the fill of a
+// range: per group copy, kq_lookup_sequence_dev over the range's maps, kq_per_base_merge_dev (which leaves the per-base array
+// zero again).  write() reads the counters once and takes the accumulator to the file like write_per_base_device.
+struct TablePasses {
+    SegmentLists segs;
+    TablePassPlan plan;
+    uint32_t* d_acc = nullptr;
+    char* d_text = nullptr;
+    kq_dbgbase* d_pb = nullptr;
+    uint64_t* d_ctr = nullptr;
+    int n_ranges = 0;
+    bool trace = false;                   // KQ_TABLE_TRACE=1
+    double t_lookup = 0, t_merge = 0;
+};
+bool table_passes_wanted(const Run& r);
+bool table_passes_begin(Run& r, TablePasses& t);
+void table_passes_range(Run& r, TablePasses& t, int lo, int hi);
+void table_passes_write(Run& r, TablePasses& t);
+
 }  // namespace kqhost

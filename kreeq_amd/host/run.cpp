@@ -105,14 +105,17 @@ void fill_range(Run& r, const std::vector<DbSource>& dbs, uint64_t read_bytes, b
 // ranges, the per-base vector is filled range by range (a position is evaluated in exactly one), a .kreeq output is written
 // range by range.  Every output is then emitted once.  With n = 1 the table stays resident afterwards, and only then the
 // outputs that need the whole graph at once read it: the variant search of -o vcf (graph_of_handle) and the device writer of
-// the per-base tables.  With n > 1 the variant search runs over the database on disk (the input one, or a temporary one
+// the per-base tables.  With n > 1 the per-base tables may accumulate on the device range by range instead of in the host vector
+// (TablePasses, opt-in), and the variant search runs over the database on disk (the input one, or a temporary one
 // written during the loop -- the reference dumps its maps to disk and reloads ranges likewise).
 void run_ranges(Run& r, const std::vector<DbSource>& dbs, uint64_t read_bytes, int n) {
     const UserInput& ui = r.ui;
     const OutPlan& plan = r.plan;
     const bool validate = ui.mode == 0, search = validate && plan.vcf && !ui.inSequence.empty();
     const bool device_tables = validate && plan.per_base && n == 1 && table_device_wanted(r);
-    const bool lookup = validate && !ui.inSequence.empty() && !plan.vcf && !device_tables;      // every other extension validates (src/kreeq-output.cpp:62-72)
+    TablePasses acc;                                                 // (taken before the first fill: the count path sizes its arena around it)
+    const bool acc_tables = validate && plan.per_base && n > 1 && table_passes_wanted(r) && table_passes_begin(r, acc);
+    const bool lookup = validate && !ui.inSequence.empty() && !plan.vcf && !device_tables && !acc_tables;      // every other extension validates (src/kreeq-output.cpp:62-72)
     if (lookup && plan.per_base) r.per_base.assign(r.genome.text.size(), kq_dbgbase{});
     // where the ranges go when a later step needs them again: the .kreeq output, or a temporary database for the variant search
     std::string range_db;
@@ -137,6 +140,10 @@ void run_ranges(Run& r, const std::vector<DbSource>& dbs, uint64_t read_bytes, i
             kq_or_die(kq_lookup_sequence(r.h, r.genome.text.data(), r.genome.text.size(), ui.covCutOff, (uint16_t)lo, (uint16_t)hi,
                                          plan.per_base ? r.per_base.data() : nullptr, r.counters));
         }
+        if (acc_tables) {
+            verbose("Validating sequence");
+            table_passes_range(r, acc, lo, hi);
+        }
         if (plan.hist) {
             uint64_t m = 0;
             kq_or_die(kq_histogram(r.h, nullptr, nullptr, 0, &m));
@@ -153,8 +160,9 @@ void run_ranges(Run& r, const std::vector<DbSource>& dbs, uint64_t read_bytes, i
     verbose("Writing ouput: " + ui.outFile);
     if (!range_db.empty()) { write_db_finish(range_db, r.k, r.map_count, hc_all); if (plan.kreeq) verbose("Database written"); }
     if (device_tables) write_per_base_device(r);
+    if (acc_tables) { table_passes_write(r, acc); print_qv(r); }
     if (lookup) print_qv(r);
-    if (validate && plan.per_base && !device_tables) write_per_base_host(r);
+    if (validate && plan.per_base && !device_tables && !acc_tables) write_per_base_host(r);
     if (plan.hist) { std::ofstream ofs(ui.outFile); for (auto& kv : hist) ofs << kv.first << "\t" << kv.second << "\n"; }
     if (search) {
         if (n == 1) write_vcf(r, graph_of_handle(r.h));
