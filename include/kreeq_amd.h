@@ -559,6 +559,37 @@ int  kq_subgraph_expand(kq_handle* db, kq_handle* sub, int depth, uint64_t* n_ad
 int  kq_subgraph_best_first(kq_handle* db, kq_handle* sub, int depth, uint32_t cov_cutoff, uint64_t* n_added);
 int  kq_subgraph_trim(kq_handle* sub, uint32_t cov_cutoff);
 
+/* kq_subgraph_gfa  The trimmed subgraph `sub` as the graph the reference hands to its GFA writer (DBG::DBGgraphToGFA and
+ * DBG::collapseNodes, src/kreeq.cpp:360-600), built on the device.  An oriented k-mer is (key, +) = the canonical string or
+ * (key, -) = its reverse complement; its id is 2 * rank of the key in ascending key order + (orientation == '-'); the
+ * out-edges of (x,+) are the non-zero fw counters, those of (x,-) the non-zero bw counters.
+ *   default          Non-branching runs become one segment each.  v -> w is a LINK when v has exactly one out-edge, w's key is
+ *       in `sub` and is another key, neither key is its own reverse complement, and flip(w) has exactly one out-edge, which
+ *       leads to flip(v).  Links form chains; a cycle is cut in front of its smallest oriented id; of a chain and its mirror
+ *       the one whose head has the smaller id is kept and is a segment.  Segments are numbered by ascending head id; the
+ *       sequence is the head's oriented k-mer plus the last base of every following one; cov is the head's.  Every other
+ *       non-zero counter whose neighbour is in `sub` is an edge: emitted when the neighbour is the first k-mer of its chain
+ *       (else counted in n_dropped_edges: asymmetric counters that point into a segment), once per bidirected pair (of an
+ *       edge and its mirror the one with the smaller (source id, target id)), in ascending (source id, base) order.  An end's
+ *       rc is 0 when the oriented k-mer lies on the kept chain.  A cycle is one segment with an edge from its + end to its + start.
+ *   KQ_GFA_NO_COLLAPSE   Every k-mer is a segment (+, numbered by ascending key); per k-mer its fw lines `this + -> next`, then
+ *       its bw lines `prev -> this +` (:545-594), nothing deduplicated; counters whose neighbour is absent give no line.
+ * The reference numbers nodes, picks the cov and orders links by the iteration order of its hash map; the numbering, cov and
+ * order here are this library's own.
+ *   segs[i]   seq + seq_off: n_kmers + k - 1 bases (no terminator); head_key / head_rc: the first oriented k-mer; cov: its cov
+ *   edges[j]  from (from_rc ? - : +) -> to (to_rc ? - : +), overlap k - 1, count = the counter that gave the edge
+ *   counts    always set on KQ_OK and KQ_ERR_CAPACITY; n_cycles = segments that were cycles
+ * segs, seq or edges NULL: only the counts.  A cap (records, bytes, records) too small: KQ_ERR_CAPACITY, nothing is written.
+ * KQ_ERR_INVALID for a null sub / counts, unknown flag bits, a windowed handle, and 2^31 or more k-mers.  An empty table:
+ * KQ_OK, all counts zero.  Flushes pending records and synchronises; device scratch (about 400 bytes per k-mer) is freed before
+ * the call returns.  The result does not depend on the launch geometry. */
+typedef struct { uint64_t seq_off, head_key; uint32_t n_kmers, cov; uint8_t head_rc, pad[7]; } kq_gfa_segment;      /* 32 bytes */
+typedef struct { uint32_t from, to, count; uint8_t from_rc, to_rc, pad[2]; } kq_gfa_edge;                           /* 16 bytes */
+typedef struct { uint64_t n_segments, n_seq, n_edges, n_dropped_edges, n_cycles; } kq_gfa_counts;
+enum { KQ_GFA_NO_COLLAPSE = 1 };
+int  kq_subgraph_gfa(kq_handle* sub, uint32_t flags, kq_gfa_segment* segs, uint64_t seg_cap, char* seq, uint64_t seq_cap,
+                     kq_gfa_edge* edges, uint64_t edge_cap, kq_gfa_counts* counts);
+
 #ifdef __cplusplus
 }
 #endif

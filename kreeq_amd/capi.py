@@ -20,7 +20,7 @@ SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profi
            "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_bgzf_scan", "kq_inflate_bgzf_dev", "kq_count_bgzf_dev", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
            "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_dev_alloc", "kq_dev_free", "kq_copy_async", "kq_per_base_triples_dev", "kq_per_base_merge_dev", "kq_format_table_dev", "kq_format_table", "kq_lookup_keys", "kq_branch_scan", "kq_search_variants", "kq_merge", "kq_import", "kq_export",
-           "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_best_first", "kq_subgraph_trim"]
+           "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_best_first", "kq_subgraph_trim", "kq_subgraph_gfa"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
 BGZF_END = 1                             # KQ_BGZF_END
@@ -29,6 +29,9 @@ TABLE_KWIG, TABLE_BED, TABLE_CSV = 1, 2, 3      # KQ_TABLE_*
 TABLE_SEG_HEADER = 1                     # KQ_TABLE_SEG_HEADER
 TABLE_SEG_DTYPE = np.dtype([("first", "<u8"), ("n", "<u8"), ("abs_pos", "<u8"), ("name_off", "<u4"), ("name_len", "<u4"), ("n_ctx", "<u4"), ("flags", "<u4")])      # kq_table_seg
 SUBGRAPH_NO_REFERENCE = 1                # KQ_SUBGRAPH_NO_REFERENCE
+GFA_NO_COLLAPSE = 1                      # KQ_GFA_NO_COLLAPSE
+GFA_SEGMENT_DTYPE = np.dtype([("seq_off", "<u8"), ("head_key", "<u8"), ("n_kmers", "<u4"), ("cov", "<u4"), ("head_rc", "u1"), ("pad", "u1", 7)])      # kq_gfa_segment
+GFA_EDGE_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("count", "<u4"), ("from_rc", "u1"), ("to_rc", "u1"), ("pad", "u1", 2)])      # kq_gfa_edge
 
 
 class KqError(RuntimeError):
@@ -40,6 +43,10 @@ class KqError(RuntimeError):
 class Stats(C.Structure):
     _fields_ = [("total", C.c_uint64), ("unique", C.c_uint64), ("distinct", C.c_uint64), ("missing", C.c_uint64),
                 ("edges", C.c_uint64)]
+
+
+class GfaCounts(C.Structure):
+    _fields_ = [("n_segments", C.c_uint64), ("n_seq", C.c_uint64), ("n_edges", C.c_uint64), ("n_dropped_edges", C.c_uint64), ("n_cycles", C.c_uint64)]
 
 
 class Info(C.Structure):
@@ -158,6 +165,7 @@ def load():
     L.kq_subgraph_expand.argtypes = [vp, vp, ci, C.POINTER(u64)]
     L.kq_subgraph_best_first.argtypes = [vp, vp, ci, u32, C.POINTER(u64)]
     L.kq_subgraph_trim.argtypes = [vp, u32]
+    L.kq_subgraph_gfa.argtypes = [vp, u32, vp, u64, vp, u64, vp, u64, C.POINTER(GfaCounts)]
     _lib = L
     return L
 
@@ -557,6 +565,27 @@ class KreeqDB:
     def subgraph_trim(self, cov_cutoff=0):
         """clears the edge counters > cov_cutoff of THIS table (a subgraph) that lead to k-mers outside it"""
         _check(load().kq_subgraph_trim(self._h, cov_cutoff))
+
+    def subgraph_gfa_raw(self, no_collapse=False, caps=None, flags=None):
+        """kq_subgraph_gfa as it is on THIS table (a subgraph): caps None = the counts only, else (seg_cap, seq_cap, edge_cap)
+        -> (return code, counts dict, segs, seq, edges); the buffers hold one element more than their cap, for the tests"""
+        cnt = GfaCounts()
+        flags = (GFA_NO_COLLAPSE if no_collapse else 0) if flags is None else flags
+        segs = seq = edges = None
+        if caps is not None:
+            segs, seq, edges = np.zeros(caps[0] + 1, dtype=GFA_SEGMENT_DTYPE), np.zeros(caps[1] + 1, dtype=np.uint8), np.zeros(caps[2] + 1, dtype=GFA_EDGE_DTYPE)
+        rc = load().kq_subgraph_gfa(self._h, flags, _p(segs), caps[0] if caps else 0, _p(seq), caps[1] if caps else 0, _p(edges), caps[2] if caps else 0, C.byref(cnt))
+        return rc, {name: int(getattr(cnt, name)) for name, _ in GfaCounts._fields_}, segs, seq, edges
+
+    def subgraph_gfa(self, no_collapse=False):
+        """THIS table (a trimmed subgraph) as a graph, built on the device (kq_subgraph_gfa): unitigs, or with no_collapse one
+        segment per k-mer -> (segs GFA_SEGMENT_DTYPE[], sequence bytes, edges GFA_EDGE_DTYPE[], counts dict).  Two calls: the
+        sizes, then the arrays."""
+        rc, counts, _, _, _ = self.subgraph_gfa_raw(no_collapse)
+        _check(rc)
+        rc, counts, segs, seq, edges = self.subgraph_gfa_raw(no_collapse, (counts["n_segments"], counts["n_seq"], counts["n_edges"]))
+        _check(rc)
+        return segs[:counts["n_segments"]], seq[:counts["n_seq"]].tobytes(), edges[:counts["n_edges"]], counts
 
     def subgraph(self, seq: bytes, depth, algorithm="traversal", no_reference=False, cov_cutoff=0):
         """seed + expand + trim -> the subgraph as a new KreeqDB.  Only the traversal runs through this binding (best-first is

@@ -34,6 +34,7 @@ using namespace kq;
 #include "kq_bgzf.h"
 #include "kq_dbimage.h"
 #include "kq_subgraph.h"
+#include "kq_gfa.h"
 #include "kq_variants.h"
 #include "kq_table.h"
 
@@ -2883,6 +2884,148 @@ int kq_subgraph_trim(kq_handle* sub, uint32_t cov_cutoff) {
     hipLaunchKernelGGL(k_sg_trim, dim3(grid_for(sub, sub->n_slots(), 256)), dim3(256), 0, sub->stream, sub->view(), cov_cutoff);
     HIPC(hipGetLastError());
     return kq_sync(sub);
+}
+
+// ---- the subgraph as a compacted graph (kq_gfa.h; reference src/kreeq.cpp:360-600) ------------------------------------------
+// With KQ_OPT_PROFILE the stages leave marks (kq_get_profile): gfa_order, gfa_links, gfa_rank_<i> for the i-th pointer-jumping
+// round of the call, gfa_cut, gfa_heads, gfa_edges, gfa_write.
+static const char* gfa_round_name(uint32_t i) {                          // 2 rankings of at most 1 + 32 rounds
+    static const std::vector<std::string> names = [] { std::vector<std::string> v; for (int j = 1; j <= 66; ++j) v.push_back("gfa_rank_" + std::to_string(j)); return v; }();
+    return names[std::min<size_t>(i, names.size() - 1)].c_str();
+}
+int kq_subgraph_gfa(kq_handle* sub, uint32_t flags, kq_gfa_segment* segs, uint64_t seg_cap, char* seq, uint64_t seq_cap, kq_gfa_edge* edges, uint64_t edge_cap,
+                    kq_gfa_counts* counts) {
+    if (!sub || !counts) return fail(KQ_ERR_INVALID, "null argument");
+    if (flags & ~(uint32_t)KQ_GFA_NO_COLLAPSE) return fail(KQ_ERR_INVALID, "unknown flags 0x%x", flags);
+    if (sub->windowed) return fail(KQ_ERR_INVALID, "subgraph calls do not take a windowed handle (KQ_OPT_BUCKET_WINDOW / KQ_OPT_SHARD_WINDOW)");
+    *counts = kq_gfa_counts{};
+    HIPC(hipSetDevice(sub->device));
+    int rc = check_errors(sub);                                          // flushes; the state says how many k-mers there are
+    if (rc) return rc;
+    const uint64_t n64 = sub->host_state()->slots_used;
+    if (n64 >= (1ull << 31)) return fail(KQ_ERR_INVALID, "subgraph of %llu k-mers: oriented k-mer ids are 32-bit (fewer than 2^31 k-mers)", (unsigned long long)n64);
+    if (!n64) return KQ_OK;
+    materialize(sub);
+    hipStream_t st = sub->stream;
+    marks_reset(sub);
+    mark(sub, "gfa_begin");
+    const uint32_t n = (uint32_t)n64, k = (uint32_t)sub->k;
+    const uint64_t n2 = 2 * n64, n_items = 4 * n2;
+    const bool collapse = !(flags & KQ_GFA_NO_COLLAPSE), want_out = segs && seq && edges;
+    DevScope mem;
+    GfaState state{};
+    GfaState* d_state = nullptr;
+    kq_entry *d_raw = nullptr, *d_ents = nullptr;
+    uint64_t* d_keys = nullptr; uint32_t* d_succ = nullptr; GfaNode* d_node[2] = {nullptr, nullptr};
+    unsigned long long *d_flag = nullptr, *d_len = nullptr, *d_seg_id = nullptr, *d_seq_off = nullptr, *d_eflag = nullptr, *d_epos = nullptr, *d_n = nullptr;
+    void* d_tmp = nullptr;
+    size_t tmp_heads = 0, tmp_items = 0;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_heads, d_flag, d_seg_id, (int64_t)(n2 + 1), st) != hipSuccess ||
+        hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_items, d_eflag, d_epos, (int64_t)(n_items + 1), st) != hipSuccess)
+        return fail(KQ_ERR_HIP, "prefix sum setup failed");
+    auto nomem = [&]() { return fail(KQ_ERR_NOMEM, "no device memory for the graph of %llu k-mers", (unsigned long long)n64); };
+    // (a) the entries in key order, their keys alone for the rank lookup
+    if (mem.alloc((void**)&d_state, sizeof(GfaState)) != hipSuccess || mem.alloc((void**)&d_n, 8) != hipSuccess || mem.alloc((void**)&d_raw, n64 * sizeof(kq_entry)) != hipSuccess) return nomem();
+    HIPC(hipMemsetAsync(d_state, 0, sizeof(GfaState), st));
+    HIPC(hipMemsetAsync(d_n, 0, 8, st));
+    hipLaunchKernelGGL(k_export, dim3(grid_for(sub, sub->n_slots(), 1024)), dim3(256), 0, st, sub->view(), (uint32_t)sub->map_count, 0u, (uint32_t)sub->map_count, d_raw, n64, d_n);
+    HIPC(hipGetLastError());
+    unsigned long long n_listed = 0;
+    HIPC(hipMemcpyAsync(&n_listed, d_n, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (n_listed != n64) return fail(KQ_ERR_HIP, "graph: %llu of %llu k-mers listed", n_listed, (unsigned long long)n64);
+    if (!sort_entries_dev(sub, mem, d_raw, n64, &d_ents)) return nomem();
+    mem.release(d_raw);
+    if (mem.alloc((void**)&d_keys, n64 * 8) != hipSuccess || mem.alloc((void**)&d_succ, n2 * 4) != hipSuccess || mem.alloc((void**)&d_node[0], n2 * sizeof(GfaNode)) != hipSuccess) return nomem();
+    hipLaunchKernelGGL(k_gfa_keys, dim3(grid_for(sub, n64, 256)), dim3(256), 0, st, (const kq_entry*)d_ents, n, d_keys);
+    mark(sub, "gfa_order");
+    int cur = 0;
+    uint32_t rounds = 0;
+    if (collapse) {
+        if (mem.alloc((void**)&d_node[1], n2 * sizeof(GfaNode)) != hipSuccess) return nomem();
+        // (b) the links
+        hipLaunchKernelGGL(k_gfa_links, dim3(grid_for(sub, n2, 256)), dim3(256), 0, st, (const kq_entry*)d_ents, (const uint64_t*)d_keys, n, k, d_succ);
+        HIPC(hipGetLastError());
+        mark(sub, "gfa_links");
+        // (c) ranking; a second time after the cycles were opened
+        uint32_t round_limit = 1;
+        while ((1ull << (round_limit - 1)) < n2) ++round_limit;          // 1 + ceil(log2(2n))
+        for (int pass = 0; pass < 2; ++pass) {
+            hipLaunchKernelGGL(k_gfa_rank_init, dim3(grid_for(sub, n2, 256)), dim3(256), 0, st, (const uint32_t*)d_succ, n, d_node[cur], d_state);
+            bool live = true;
+            for (uint32_t r = 0; r < round_limit && live; ++r) {
+                HIPC(hipMemsetAsync(&d_state->changed, 0, sizeof(unsigned int), st));
+                hipLaunchKernelGGL(k_gfa_rank_round, dim3(grid_for(sub, n2, 256)), dim3(256), 0, st, (const GfaNode*)d_node[cur], d_node[cur ^ 1], n, d_state);
+                HIPC(hipGetLastError());
+                mark(sub, gfa_round_name(rounds++));
+                cur ^= 1;
+                HIPC(hipMemcpyAsync(&state, d_state, sizeof state, hipMemcpyDeviceToHost, st));      // only the changed flag and the error mask return to the host
+                HIPC(hipStreamSynchronize(st));
+                if (state.err) return fail(KQ_ERR_HIP, "graph: a chain pointer left its bounds (error mask %u)", state.err);
+                live = state.changed != 0;
+            }
+            if (!live) break;
+            if (pass == 1) return fail(KQ_ERR_HIP, "graph: the chains did not rank in %u rounds after the cycles were opened", round_limit);
+            hipLaunchKernelGGL(k_gfa_cut, dim3(grid_for(sub, n2, 256)), dim3(256), 0, st, (const GfaNode*)d_node[cur], n, d_succ, d_state);
+            HIPC(hipGetLastError());
+            mark(sub, "gfa_cut");
+        }
+        mem.release(d_node[cur ^ 1]);
+        d_node[cur ^ 1] = nullptr;
+    } else {                                                             // (f) every oriented k-mer is a chain of its own
+        HIPC(hipMemsetAsync(d_succ, 0xFF, n2 * 4, st));
+        hipLaunchKernelGGL(k_gfa_rank_init, dim3(grid_for(sub, n2, 256)), dim3(256), 0, st, (const uint32_t*)d_succ, n, d_node[0], d_state);
+    }
+    const GfaNode* d_rank = d_node[cur];
+    // (d) segment ids and sequence offsets
+    if (mem.alloc((void**)&d_flag, (n2 + 1) * 8) != hipSuccess || mem.alloc((void**)&d_len, (n2 + 1) * 8) != hipSuccess || mem.alloc((void**)&d_seg_id, (n2 + 1) * 8) != hipSuccess ||
+        mem.alloc((void**)&d_seq_off, (n2 + 1) * 8) != hipSuccess || mem.alloc(&d_tmp, std::max(tmp_heads, tmp_items)) != hipSuccess)
+        return nomem();
+    hipLaunchKernelGGL(k_gfa_heads, dim3(grid_for(sub, n2 + 1, 256)), dim3(256), 0, st, d_rank, n, k, d_flag, d_len, d_state);
+    HIPC(hipGetLastError());
+    HIPC(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_heads, d_flag, d_seg_id, (int64_t)(n2 + 1), st));
+    HIPC(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_heads, d_len, d_seq_off, (int64_t)(n2 + 1), st));
+    HIPC(hipStreamSynchronize(st));                                      // the scans read what is released here
+    mem.release(d_flag); mem.release(d_len);
+    mark(sub, "gfa_heads");
+    // (e) the edges: flags, then their places
+    if (mem.alloc((void**)&d_eflag, (n_items + 1) * 8) != hipSuccess || mem.alloc((void**)&d_epos, (n_items + 1) * 8) != hipSuccess) return nomem();
+    hipLaunchKernelGGL(k_gfa_edges<false>, dim3(grid_for(sub, n_items + 1, 256)), dim3(256), 0, st, (const kq_entry*)d_ents, (const uint64_t*)d_keys, (const uint32_t*)d_succ, d_rank,
+                       (const unsigned long long*)d_seg_id, n, k, (uint32_t)collapse, d_eflag, (const unsigned long long*)nullptr, (kq_gfa_edge*)nullptr, 0ull, d_state);
+    HIPC(hipGetLastError());
+    HIPC(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_items, d_eflag, d_epos, (int64_t)(n_items + 1), st));
+    unsigned long long n_segs = 0, n_seq = 0, n_edges = 0;
+    mark(sub, "gfa_edges");
+    HIPC(hipMemcpyAsync(&n_segs, d_seg_id + n2, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&n_seq, d_seq_off + n2, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&n_edges, d_epos + n_items, 8, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(&state, d_state, sizeof state, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (state.err) return fail(KQ_ERR_HIP, "graph: a chain left its bounds (error mask %u)", state.err);
+    counts->n_segments = n_segs; counts->n_seq = n_seq; counts->n_edges = n_edges; counts->n_dropped_edges = state.n_dropped; counts->n_cycles = state.n_cycles;
+    if (!want_out) return KQ_OK;
+    if (n_segs > seg_cap || n_seq > seq_cap || n_edges > edge_cap)
+        return fail(KQ_ERR_CAPACITY, "%llu segments with %llu bases and %llu links: the buffers hold %llu, %llu and %llu", n_segs, n_seq, n_edges, (unsigned long long)seg_cap,
+                    (unsigned long long)seq_cap, (unsigned long long)edge_cap);
+    // the records and the bases
+    mem.release(d_eflag);
+    kq_gfa_segment* d_segs = nullptr; char* d_seq = nullptr; kq_gfa_edge* d_edges = nullptr;
+    if (mem.alloc((void**)&d_segs, n_segs * sizeof(kq_gfa_segment)) != hipSuccess || mem.alloc((void**)&d_seq, n_seq) != hipSuccess || mem.alloc((void**)&d_edges, n_edges * sizeof(kq_gfa_edge)) != hipSuccess)
+        return nomem();
+    hipLaunchKernelGGL(k_gfa_segments, dim3(grid_for(sub, n2, 256)), dim3(256), 0, st, (const kq_entry*)d_ents, d_rank, n, k, (const unsigned long long*)d_seg_id,
+                       (const unsigned long long*)d_seq_off, d_segs, (uint64_t)n_segs, d_seq, (uint64_t)n_seq, d_state);
+    hipLaunchKernelGGL(k_gfa_edges<true>, dim3(grid_for(sub, n_items + 1, 256)), dim3(256), 0, st, (const kq_entry*)d_ents, (const uint64_t*)d_keys, (const uint32_t*)d_succ, d_rank,
+                       (const unsigned long long*)d_seg_id, n, k, (uint32_t)collapse, (unsigned long long*)nullptr, (const unsigned long long*)d_epos, d_edges, (uint64_t)n_edges, d_state);
+    HIPC(hipGetLastError());
+    mark(sub, "gfa_write");
+    HIPC(hipMemcpyAsync(&state, d_state, sizeof state, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    if (state.err) return fail(KQ_ERR_HIP, "graph: a record left its bounds (error mask %u)", state.err);      // cannot happen: the totals are the scans'
+    hipError_t e1 = n_segs ? copy_out_bounced(sub, segs, d_segs, n_segs * sizeof(kq_gfa_segment)) : hipSuccess;
+    hipError_t e2 = n_seq ? copy_out_bounced(sub, seq, d_seq, n_seq) : hipSuccess;
+    hipError_t e3 = n_edges ? copy_out_bounced(sub, edges, d_edges, n_edges * sizeof(kq_gfa_edge)) : hipSuccess;
+    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(KQ_ERR_HIP, "graph: copy out failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2 != hipSuccess ? e2 : e3));
+    return KQ_OK;
 }
 
 }  // extern "C"

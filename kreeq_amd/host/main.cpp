@@ -11,6 +11,7 @@
 #include <stdexcept>
 
 #include "cli_common.h"
+#include "cli_plan.h"
 #include "fastx.h"
 #include "kreeq_db.h"
 
@@ -75,9 +76,9 @@ void print_mode_help(int mode) {
         printf("\t-f --input-sequence sequence input file (fasta).\n");
         printf("\t--traversal-algorithm <string> the approach used for graph search (best-first/traversal, default: best-first).\n");
         printf("\t--search-depth the max depth for graph traversal (default: k for best-first, ceil(k / 2) for traversal; traversal: at most 255).\n");
-        printf("\t--no-collapse accepted; no effect (the GFA model and its linear-node collapse are not built).\n");
+        printf("\t--no-collapse do not collapse linear nodes (takes effect with KQ_SUBGRAPH_GFA=1, which builds the graph; no effect otherwise).\n");
         printf("\t--no-reference do not include reference nodes (default: false).\n");
-        printf("\t-o --out-format not supported by this build (the GFA writer is not built): refused.\n");
+        printf("\t-o --out-format with KQ_SUBGRAPH_GFA=1: <name>.gfa, the subgraph as GFA 1 (no .gfa.gz / .gfa2); refused otherwise.\n");
         printf("\t-p --input-positions not supported by this build: refused.\n");
         printf("\t-j --threads <n> accepted for compatibility.\n");
         printf("\t-m --max-memory <GB> HBM the database table may use (default: 60 %% of what is free).\n");
@@ -231,7 +232,12 @@ int main(int argc, char** argv) {
     if (ui.mode == 2) {
         if (ui.kmerDB.size() != 1) { fprintf(stderr, "Need to provide one database (-d).\n"); return EXIT_FAILURE; }   // src/main.cpp:413-416
         if (!ui.inBedInclude.empty()) { fprintf(stderr, "Error: -p / --input-positions is not supported by this build (BED paths to segments are not built).\n"); return EXIT_FAILURE; }
-        if (!ui.outFile.empty()) { fprintf(stderr, "Error: -o %s: subgraph output files (GFA) are not supported by this build; the summary goes to stdout.\n", ui.outFile.c_str()); return EXIT_FAILURE; }
+        // KQ_SUBGRAPH_GFA=1 (off by default): the graph is built on the GPU (kq_subgraph_gfa), its block printed and -o <name>.gfa written
+        if (!ui.outFile.empty() && !env_flag("KQ_SUBGRAPH_GFA")) { fprintf(stderr, "Error: -o %s: subgraph output files (GFA) are not supported by this build; the summary goes to stdout.\n", ui.outFile.c_str()); return EXIT_FAILURE; }
+        if (!ui.outFile.empty() && !(ui.outFile.find('.') != std::string::npos && file_ext(ui.outFile) == "gfa")) {
+            fprintf(stderr, "Error: -o %s: subgraph mode writes <name>.gfa only (GFA 1, uncompressed).\n", ui.outFile.c_str());
+            return EXIT_FAILURE;
+        }
         if (ui.travAlgorithm != "best-first" && ui.travAlgorithm != "traversal") {       // src/subgraph.cpp:296
             fprintf(stderr, "Cannot find input algorithm (%s). Terminating.\n", ui.travAlgorithm.c_str());
             return EXIT_FAILURE;

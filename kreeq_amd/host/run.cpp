@@ -12,6 +12,7 @@
 #include "db_source.h"
 #include "per_base.h"
 #include "subgraph.h"
+#include "gfa_out.h"
 
 namespace kqhost {
 
@@ -290,8 +291,36 @@ void run_subgraph(Run& r) {                                          // src/inpu
     kq_stats st;
     kq_or_die(kq_summary(sub, &st));
     print_stats("Subgraph summary statistics:", st);                 // DBG::summary(ParallelMap32color&), :163-188
+    // KQ_SUBGRAPH_GFA=1 (off by default): the graph of DBG::DBGgraphToGFA (src/kreeq.cpp:523-600) is built on the GPU
+    // (kq_subgraph_gfa); its "+++Assembly summary+++" block goes between the two summaries and -o <name>.gfa is written.
+    // Without it nothing is printed here (gfalibs' report of its GFA model).
+    if (env_flag("KQ_SUBGRAPH_GFA")) {
+        const uint32_t flags = ui.noCollapse ? KQ_GFA_NO_COLLAPSE : 0;
+        kq_gfa_counts cnt{};
+        GfaGraph g;
+        g.k = r.k;
+        kq_or_die(kq_subgraph_gfa(sub, flags, nullptr, 0, nullptr, 0, nullptr, 0, &cnt));
+        g.segs.resize(cnt.n_segments); g.seq.resize(cnt.n_seq); g.edges.resize(cnt.n_edges);
+        // (the vectors' data() may be null when empty: one element of room keeps "the arrays are wanted" apart from "counts only")
+        kq_gfa_segment seg0{}; kq_gfa_edge edge0{}; char seq0 = 0;
+        kq_or_die(kq_subgraph_gfa(sub, flags, g.segs.empty() ? &seg0 : g.segs.data(), cnt.n_segments, g.seq.empty() ? &seq0 : &g.seq[0], cnt.n_seq,
+                                  g.edges.empty() ? &edge0 : g.edges.data(), cnt.n_edges, &cnt));
+        step("gfa");
+        verbose("subgraph GFA built on the device: " + std::to_string(cnt.n_segments) + " segments, " + std::to_string(cnt.n_edges) + " links, " +
+                std::to_string(cnt.n_dropped_edges) + " links dropped, " + std::to_string(cnt.n_cycles) + " cycles");
+        if (!gfa_valid(g)) die("Error: the device returned a graph whose records leave their arrays");
+        std::string text;
+        gfa_block(gfa_stats(g), text);
+        fwrite(text.data(), 1, text.size(), stdout);
+        if (!ui.outFile.empty()) {
+            text.clear();
+            gfa_text(g, text);
+            FILE* f = fopen(ui.outFile.c_str(), "wb");
+            if (!f || fwrite(text.data(), 1, text.size(), f) != text.size() || fclose(f) != 0) die("Error: cannot write " + ui.outFile);
+            verbose("Graph written to " + ui.outFile);
+        }
+    }
     kq_destroy(sub);
-    // (the reference prints gfalibs' "+++Assembly summary+++" of the GFA model here: not built)
     kq_or_die(kq_summary(r.h, &st));                                 // DBG::report with no -o, src/kreeq-output.cpp:34-60
     print_dbg_stats(st);
 }
