@@ -299,6 +299,24 @@ int  kq_inflate_bgzf_dev(kq_handle* h, const void* d_comp, uint64_t comp_len, co
                          char* d_text, uint64_t cap, uint64_t* n_text);
 int  kq_count_bgzf_dev(kq_handle* h, const void* d_comp, uint64_t comp_len, const kq_bgzf_block* blocks, uint64_t n_blocks, int format, uint32_t flags);
 
+/* Text -> BGZF, the other direction: the text is cut into members of 0xff00 bytes (bgzip's choice; the last one shorter), every
+ * member is compressed by one wave on the GPU (LZ77 with a hash table in LDS, one dynamic-Huffman block, or one stored block when
+ * that is not smaller: no member is larger than 18 + 5 + its text + 8 bytes), and the members lie back to back in the output.
+ * The bytes are a function of the text alone: not of the alignment of d_text, the launch geometry or the schedule.
+ *   kq_bgzf_bound        host only: the largest output kq_deflate_bgzf_dev can produce for n_text bytes with these flags
+ *                        (n_text + 31 per member, + 28 with KQ_BGZF_EOF).
+ *   kq_deflate_bgzf_dev  d_text (device, any alignment) -> d_out (device, any alignment, room for cap bytes); *n_out = the bytes
+ *                        written.  KQ_BGZF_EOF appends the standard 28-byte empty member that ends a BGZF file.  cap below
+ *                        kq_bgzf_bound: KQ_ERR_CAPACITY with *n_out = the bound, before any device work.  n_text == 0 writes
+ *                        nothing, or only the marker.  The outputs of successive calls, concatenated, are one valid BGZF file.
+ *                        Runs on the handle's stream and synchronises; one caller at a time, like the entries above.
+ *   kq_deflate_bgzf      the same from and to HOST buffers (staging, the device call, the copy back): tests and small callers.
+ * Null pointers (h, n_out; d_text with n_text, d_out with cap) or unknown flag bits: KQ_ERR_INVALID before any device work. */
+enum { KQ_BGZF_EOF = 2 };
+uint64_t kq_bgzf_bound(uint64_t n_text, uint32_t flags);
+int  kq_deflate_bgzf_dev(kq_handle* h, const char* d_text, uint64_t n_text, void* d_out, uint64_t cap, uint64_t* n_out, uint32_t flags);
+int  kq_deflate_bgzf(kq_handle* h, const char* text, uint64_t n_text, void* out, uint64_t cap, uint64_t* n_out, uint32_t flags);
+
 /* Hot loop 1 only (DBG::hashSequences :75-113): the (key, edge byte) records of a batch in
  * sequence order; edge byte layout = edgeBit (include/kreeq.h:6-18).  *n_out = number of records
  * (also set on KQ_ERR_CAPACITY).  keys/edges may be NULL to just count. */

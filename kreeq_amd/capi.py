@@ -17,13 +17,15 @@ ERR_CAPACITY = -6                        # KQ_ERR_CAPACITY
 # every symbol include/kreeq_amd.h declares
 SYMBOLS = ["kq_create", "kq_destroy", "kq_clear", "kq_set_option", "kq_get_profile", "kq_set_stream", "kq_get_stream", "kq_sync", "kq_flush", "kq_get_info", "kq_last_error",
            "kq_abi_version", "kq_device_available", "kq_device_memory", "kq_count_batch", "kq_count_batch_dev", "kq_host_alloc", "kq_host_free", "kq_count_batch_async", "kq_host_wait", "kq_pack_bases", "kq_count_packed_dev", "kq_count_packed_async",
-           "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_bgzf_scan", "kq_inflate_bgzf_dev", "kq_count_bgzf_dev", "kq_emit_records",
+           "kq_pack_bases_dev", "kq_parse_fastx_dev", "kq_count_fastx_dev", "kq_count_fastx_async", "kq_bgzf_scan", "kq_inflate_bgzf_dev", "kq_count_bgzf_dev", "kq_bgzf_bound", "kq_deflate_bgzf_dev", "kq_deflate_bgzf", "kq_emit_records",
            "kq_emit_partitioned_dev", "kq_emit_packed_dev", "kq_insert_packed_dev", "kq_emit_sharded_dev", "kq_insert_sharded_dev", "kq_emit_sharded8_dev", "kq_insert_sharded8_dev", "kq_insert_records", "kq_insert_records_dev", "kq_summary", "kq_histogram",
            "kq_lookup_sequence", "kq_lookup_sequence_dev", "kq_dev_alloc", "kq_dev_free", "kq_copy_async", "kq_per_base_triples_dev", "kq_per_base_merge_dev", "kq_format_table_dev", "kq_format_table", "kq_lookup_keys", "kq_branch_scan", "kq_search_variants", "kq_merge", "kq_import", "kq_export",
            "kq_export_map_images", "kq_import_map_image", "kq_subgraph_seed", "kq_subgraph_seed_dev", "kq_subgraph_expand", "kq_subgraph_best_first", "kq_subgraph_trim", "kq_subgraph_gfa"]
 
 FASTX_FASTQ, FASTX_FASTA = 1, 2          # KQ_FASTX_FASTQ / KQ_FASTX_FASTA
 BGZF_END = 1                             # KQ_BGZF_END
+BGZF_EOF = 2                             # KQ_BGZF_EOF
+BGZF_MEMBER_TEXT = 0xff00                # text bytes per member written by deflate_bgzf
 BGZF_BLOCK_DTYPE = np.dtype([("off", "<u8"), ("size", "<u4"), ("data_off", "<u4"), ("data_len", "<u4"), ("crc32", "<u4"), ("isize", "<u4"), ("pad", "<u4")])      # kq_bgzf_block
 TABLE_KWIG, TABLE_BED, TABLE_CSV = 1, 2, 3      # KQ_TABLE_*
 TABLE_SEG_HEADER = 1                     # KQ_TABLE_SEG_HEADER
@@ -129,6 +131,10 @@ def load():
     L.kq_bgzf_scan.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.kq_inflate_bgzf_dev.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]
     L.kq_count_bgzf_dev.argtypes = [vp, vp, u64, vp, u64, ci, u32]
+    L.kq_bgzf_bound.argtypes = [u64, u32]
+    L.kq_bgzf_bound.restype = u64
+    L.kq_deflate_bgzf_dev.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
+    L.kq_deflate_bgzf.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32]
     L.kq_emit_records.argtypes = [vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.kq_emit_partitioned_dev.argtypes = [vp, vp, u64, ci, vp, vp, u64, vp]
     L.kq_emit_packed_dev.argtypes = [vp, vp, u64, ci, vp, u64, vp]
@@ -186,6 +192,11 @@ def pack_bases(bases: bytes):
     codes, inv = np.zeros(max(units, 1), dtype=np.uint32), np.zeros(max(units, 1), dtype=np.uint16)
     load().kq_pack_bases(_p(buf) if len(buf) else None, len(buf), _p(codes), _p(inv))
     return codes[:units], inv[:units]
+
+
+def bgzf_bound(n_text, flags=0):
+    """the largest output deflate_bgzf / deflate_bgzf_dev can produce for n_text bytes (kq_bgzf_bound; host only)"""
+    return int(load().kq_bgzf_bound(n_text, flags))
 
 
 def bgzf_scan(data: bytes, cap=None):
@@ -332,6 +343,30 @@ class KreeqDB:
             e.needed = nt.value
             raise e
         return nt.value
+
+    def deflate_bgzf_dev(self, text_ptr, n_text, out_ptr, cap, flags=0):
+        """device text -> BGZF members at out_ptr (device, room for cap bytes); returns the bytes written.  flags = BGZF_EOF
+        appends the end-of-file marker.  Raises KqError -6 when cap is below bgzf_bound(n_text, flags) (KqError.needed holds it)"""
+        no = C.c_uint64(0)
+        rc = load().kq_deflate_bgzf_dev(self._h, C.c_void_p(text_ptr) if text_ptr else None, n_text, C.c_void_p(out_ptr) if out_ptr else None, cap, C.byref(no), flags)
+        if rc != 0:
+            e = KqError(rc, load().kq_last_error().decode(errors="replace"))
+            e.needed = no.value
+            raise e
+        return no.value
+
+    def deflate_bgzf(self, text: bytes, flags=0, cap=None):
+        """host text -> its BGZF members as bytes (kq_deflate_bgzf: staging, the device call, the copy back)"""
+        src = np.frombuffer(text, dtype=np.uint8)
+        room = bgzf_bound(len(src), flags) if cap is None else cap
+        out = np.empty(max(room, 1), dtype=np.uint8)
+        no = C.c_uint64(0)
+        rc = load().kq_deflate_bgzf(self._h, _p(src) if len(src) else None, len(src), _p(out) if room else None, room, C.byref(no), flags)
+        if rc != 0:
+            e = KqError(rc, load().kq_last_error().decode(errors="replace"))
+            e.needed = no.value
+            raise e
+        return out[:no.value].tobytes()
 
     def count_bgzf_dev(self, comp_ptr, comp_len, blocks, fmt, flags=0):
         """one piece of a BGZF stream from device memory: inflate behind the carry, count the whole records, keep the rest;

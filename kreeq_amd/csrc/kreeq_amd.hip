@@ -32,6 +32,7 @@ using namespace kq;
 #include "kq_kernels.h"
 #include "kq_fastx.h"
 #include "kq_bgzf.h"
+#include "kq_deflate.h"
 #include "kq_dbimage.h"
 #include "kq_subgraph.h"
 #include "kq_gfa.h"
@@ -232,6 +233,10 @@ struct kq_handle {
     // mirror, the text of one call (carry + the call's members) and the carry of a kq_count_bgzf_dev stream between calls
     DevMem bz_desc, bz_stat, bz_text, bz_carry;
     PinnedMem bz_desc_host, bz_stat_host;
+    // the BGZF writer (kq_deflate.h): a batch's member slots, their sizes and output offsets, the status record and its mirror,
+    // and the staging of the host-buffer form
+    DevMem df_slots, df_sizes, df_offs, df_stat, df_in, df_out;
+    PinnedMem df_stat_host;
     uint64_t bz_carry_len = 0;
     bool bz_bad = false;                 // a counted BGZF member was corrupt: reported by kq_sync until kq_clear
     std::string bz_err;                  // its message
@@ -1587,6 +1592,80 @@ int kq_inflate_bgzf_dev(kq_handle* h, const void* d_comp, uint64_t comp_len, con
     rc = bz_read_status(h, h->stream); if (rc) return rc;
     const BzStatus* s = h->bz_stat_host.as<BzStatus>();
     if (s->first_bad != ~0ull) return fail(KQ_ERR_INVALID, "%s", bz_describe(s).c_str());
+    return KQ_OK;
+}
+
+// ---- text -> BGZF members on the device (kq_deflate.h, kq_deflate_core.h) ---------------------------------------------------
+
+constexpr uint64_t DF_BATCH = 4096;      // members per launch: 256 MiB of slots at the most
+
+uint64_t kq_bgzf_bound(uint64_t n_text, uint32_t flags) {
+    const uint64_t members = (n_text + kqdef::MEMBER_TEXT - 1) / kqdef::MEMBER_TEXT;
+    return n_text + members * (kqdef::HEADER_BYTES + kqdef::STORED_BYTES + kqdef::TRAILER_BYTES) + ((flags & KQ_BGZF_EOF) ? kqdef::EOF_BYTES : 0);
+}
+
+int kq_deflate_bgzf_dev(kq_handle* h, const char* d_text, uint64_t n_text, void* d_out, uint64_t cap, uint64_t* n_out, uint32_t flags) {
+    if (!h || !n_out || (!d_text && n_text) || (!d_out && cap)) return fail(KQ_ERR_INVALID, "null argument");
+    *n_out = 0;
+    if (flags & ~(uint32_t)KQ_BGZF_EOF) return fail(KQ_ERR_INVALID, "unknown flag bits %#x", flags);
+    const uint64_t bound = kq_bgzf_bound(n_text, flags);
+    if (cap < bound) { *n_out = bound; return fail(KQ_ERR_CAPACITY, "output buffer too small: up to %llu bytes of BGZF, room for %llu", (unsigned long long)bound, (unsigned long long)cap); }
+    if (!bound) return KQ_OK;
+    HIPC(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const uint64_t members = (n_text + kqdef::MEMBER_TEXT - 1) / kqdef::MEMBER_TEXT, batch = std::min(members, DF_BATCH);
+    uint64_t total = 0;
+    if (members) {
+        if (!h->df_stat) HIPC(h->df_stat.alloc(sizeof(DfStatus)));
+        if (!h->df_stat_host) HIPC(h->df_stat_host.alloc(sizeof(DfStatus)));
+        HIPC(h->df_slots.ensure((size_t)batch * DF_SLOT));
+        HIPC(h->df_sizes.ensure((size_t)batch * sizeof(uint32_t)));
+        HIPC(h->df_offs.ensure((size_t)batch * sizeof(unsigned long long)));
+        HIPC(hipMemsetAsync(h->df_stat.get(), 0xFF, sizeof(unsigned long long), st));                                  // no bad member
+        HIPC(hipMemsetAsync(h->df_stat.as<char>() + sizeof(unsigned long long), 0, sizeof(unsigned long long), st));   // nothing written
+        for (uint64_t m0 = 0; m0 < members; m0 += batch) {
+            const uint32_t nm = (uint32_t)std::min(batch, members - m0);
+            hipLaunchKernelGGL(k_bgzf_deflate, dim3(nm), dim3(64), 0, st, (const uint8_t*)d_text, n_text, m0, nm, h->df_slots.as<uint8_t>(), h->df_sizes.as<uint32_t>(),
+                               h->df_stat.as<DfStatus>());
+            hipLaunchKernelGGL(k_bgzf_sizes_scan, dim3(1), dim3(64), 0, st, h->df_sizes.as<const uint32_t>(), nm, h->df_offs.as<unsigned long long>(), h->df_stat.as<DfStatus>());
+            hipLaunchKernelGGL(k_bgzf_gather, dim3(nm), dim3(DF_GATHER_THREADS), 0, st, h->df_slots.as<const uint8_t>(), h->df_sizes.as<const uint32_t>(),
+                               h->df_offs.as<const unsigned long long>(), nm, (uint8_t*)d_out);
+            HIPC(hipGetLastError());
+        }
+        HIPC(hipMemcpyAsync(h->df_stat_host.get(), h->df_stat.get(), sizeof(DfStatus), hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        const DfStatus* s = h->df_stat_host.as<DfStatus>();
+        if (s->first_bad != ~0ull)
+            return fail(KQ_ERR_INVALID, "BGZF member %llu could not be written (%s)", s->first_bad >> 8, kqdef::err_name((int)(s->first_bad & 0xFF)));
+        total = s->total;
+        if (total + ((flags & KQ_BGZF_EOF) ? kqdef::EOF_BYTES : 0) > bound) return fail(KQ_ERR_INVALID, "the BGZF writer produced %llu bytes, above its bound %llu", (unsigned long long)total, (unsigned long long)bound);
+    }
+    if (flags & KQ_BGZF_EOF) {
+        static uint8_t eof[kqdef::EOF_BYTES];
+        for (uint32_t i = 0; i < kqdef::EOF_BYTES; ++i) eof[i] = (uint8_t)kqdef::eof_byte(i);
+        HIPC(hipMemcpyAsync((uint8_t*)d_out + total, eof, kqdef::EOF_BYTES, hipMemcpyHostToDevice, st));
+        HIPC(hipStreamSynchronize(st));
+        total += kqdef::EOF_BYTES;
+    }
+    *n_out = total;
+    return KQ_OK;
+}
+
+int kq_deflate_bgzf(kq_handle* h, const char* text, uint64_t n_text, void* out, uint64_t cap, uint64_t* n_out, uint32_t flags) {
+    if (!h || !n_out || (!text && n_text) || (!out && cap)) return fail(KQ_ERR_INVALID, "null argument");
+    *n_out = 0;
+    if (flags & ~(uint32_t)KQ_BGZF_EOF) return fail(KQ_ERR_INVALID, "unknown flag bits %#x", flags);
+    const uint64_t bound = kq_bgzf_bound(n_text, flags);
+    if (cap < bound) { *n_out = bound; return fail(KQ_ERR_CAPACITY, "output buffer too small: up to %llu bytes of BGZF, room for %llu", (unsigned long long)bound, (unsigned long long)cap); }
+    if (!bound) return KQ_OK;
+    HIPC(hipSetDevice(h->device));
+    HIPC(h->df_in.ensure((size_t)n_text + 16));
+    HIPC(h->df_out.ensure((size_t)bound));
+    if (n_text) HIPC(hipMemcpyAsync(h->df_in.get(), text, (size_t)n_text, hipMemcpyHostToDevice, h->stream));
+    const int rc = kq_deflate_bgzf_dev(h, h->df_in.as<const char>(), n_text, h->df_out.get(), bound, n_out, flags);
+    if (rc) return rc;
+    HIPC(hipMemcpyAsync(out, h->df_out.get(), (size_t)*n_out, hipMemcpyDeviceToHost, h->stream));
+    HIPC(hipStreamSynchronize(h->stream));
     return KQ_OK;
 }
 

@@ -30,12 +30,18 @@ struct OutPlan {
     bool want_stats = true, want_qv = true;                     // the summary block; the QV table of a validation
     bool per_base = false, vcf = false, kreeq = false, hist = false;
     bool refused = false;                                       // validate -o x.gfa*: the variant graph is not built
+    bool table_gz = false;                                      // x.kwig.gz / x.bed.gz / x.csvtable.gz: the text table as BGZF; per_base stays
+    std::string table_ext;                                      // false and ext keeps its ".gz"; table_ext is the format inside
+    bool tables() const { return per_base || table_gz; }        // a per-base file is written, plain or compressed
+    const std::string& table_format() const { return table_gz ? table_ext : ext; }
 };
 inline OutPlan plan_output(int mode, const std::string& out_file) {
     OutPlan p;
     if (out_file != "") p.ext = file_ext("." + out_file);
     p.kreeq = p.ext == "kreeq"; p.vcf = p.ext == "vcf"; p.hist = p.ext == "hist";
     p.per_base = p.ext == "kwig" || p.ext == "bkwig" || p.ext == "bed" || p.ext == "csvtable";
+    p.table_gz = p.ext == "kwig.gz" || p.ext == "bed.gz" || p.ext == "csvtable.gz";      // (.bkwig is binary and compact already: no .bkwig.gz)
+    if (p.table_gz) p.table_ext = p.ext.substr(0, p.ext.size() - 3);
     p.want_qv = out_file.find(".") != std::string::npos || out_file == "";
     p.want_stats = p.want_qv || p.kreeq;
     p.refused = mode == 0 && (p.ext == "gfa" || p.ext == "gfa2" || p.ext == "gfa.gz" || p.ext == "gfa2.gz");

@@ -62,6 +62,7 @@ void print_mode_help(int mode) {
         printf("\t-k --kmer-length length of kmers.\n");
         printf("\t-o --out-format supported extensions:\n");
         printf("\t\t .kreeq dumps hashmaps to file for reuse; .kwig .bkwig per-base tables; .hist coverage histogram.\n");
+        printf("\t\t .kwig.gz .bed.gz .csvtable.gz the text tables as BGZF (bgzip-compatible).\n");
         printf("\t-t --tmp-prefix prefix to temporary directory (unused: the table lives in HBM).\n");
         printf("\t-m --max-memory <GB> HBM the k-mer table may use (default: 60 %% of what is free); bounds the map ranges counted at a time.\n");
         printf("\t-j --threads <n> parser threads for the read files (default: all cores).\n");

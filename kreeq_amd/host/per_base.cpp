@@ -3,6 +3,8 @@
 // table, or accumulated over map ranges.
 #include "per_base.h"
 
+#include "bgzf_out.h"
+
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -23,9 +25,9 @@ double error_rate(uint64_t missing, uint64_t total, int k) { return 1 - pow(1 - 
 const kq_dbgbase* bases_of(const Run& r, size_t s, uint64_t seg_start) { return r.per_base.data() + r.genome.offset[s] + seg_start; }
 
 // .kwig (src/kreeq-output.cpp:243-303) and .bkwig (:305-399)
-void write_kwig(const Run& r, const SegmentLists& segs) {
-    std::ofstream ofs(r.ui.outFile);
+void write_kwig(const Run& r, const SegmentLists& segs, std::ostream& ofs, BgzfBuf* gz) {
     ofs << std::to_string(r.k) << "\n";
+    if (gz) gz->cut();                                                   // the head line is a member of its own, as the device writer has it
     for (size_t s = 0; s < r.seqs.size(); ++s)
         for (auto& seg : segs[s]) {
             ofs << "fixedStep chrom=" << r.seqs[s].header << " start=" << seg.first << " step=1" << "\n";
@@ -71,11 +73,10 @@ void write_bkwig(const Run& r, const SegmentLists& segs) {
 // .bed / .csvtable per-base table (src/kreeq-output.cpp:138-241): for every position the k most
 // recent values of cov / fw-edge / bw-edge, oldest first.  No fixture of the reference pins this
 // text (parity unpinned); it is restated from the writer's source.
-void write_table(const Run& r, const SegmentLists& segs) {
+void write_table(const Run& r, const SegmentLists& segs, std::ostream& ofs) {
     const int k = r.k;
     char colSep = ',', entrySep = ',';
-    if (r.plan.ext == "bed") colSep = '\t', entrySep = ':';
-    std::ofstream ofs(r.ui.outFile);
+    if (r.plan.table_format() == "bed") colSep = '\t', entrySep = ':';
     for (size_t s = 0; s < r.seqs.size(); ++s)
         for (auto& seg : segs[s]) {
             std::vector<uint32_t> kc(k - 1, 0), ef(k - 1, 0), eb(k - 1, 0);
@@ -139,7 +140,8 @@ struct TableOut {
 // "Triples on the device -> file", the half that both device paths share: the file with its head (.kwig's k, .bkwig's index),
 // and per call -- sequences [lo, hi), whose triples lie segment after segment at d_triples -- the payload copied out as it is
 // (.bkwig) or formatted in chunks of at most KQ_TABLE_CHUNK_LINES positions (cut_table_chunks + kq_format_table_dev), through
-// the two page-locked buffers of TableOut.
+// the two page-locked buffers of TableOut.  With a .gz name every formatted chunk is deflated on the device into BGZF members
+// (kq_deflate_bgzf_dev) and only those cross to the host; the head line is a member of its own, finish() writes the marker.
 struct DeviceTableFile {
     const Run& r;
     kq_handle* h;
@@ -151,19 +153,35 @@ struct DeviceTableFile {
     std::vector<uint32_t> name_off;
     char* d_text = nullptr;
     uint64_t d_text_cap = 0;
-    double t_format = 0, t_copy = 0;
+    const bool gz;                                                   // BGZF members instead of text
+    char* d_gz = nullptr;
+    uint64_t d_gz_cap = 0, text_bytes = 0;
+    double t_format = 0, t_copy = 0, t_deflate = 0;
     static int format_of(const std::string& ext) { return ext == "kwig" ? KQ_TABLE_KWIG : ext == "bed" ? KQ_TABLE_BED : ext == "csvtable" ? KQ_TABLE_CSV : 0; }
-    DeviceTableFile(const Run& run, const SegmentLists& sl) : r(run), h(run.h), segs(sl), fmt(format_of(run.plan.ext)) {
+    DeviceTableFile(const Run& run, const SegmentLists& sl) : r(run), h(run.h), segs(sl), fmt(format_of(run.plan.table_format())), gz(run.plan.table_gz) {
         out.fd = ::open(r.ui.outFile.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
         if (out.fd < 0) die("Error: cannot write " + r.ui.outFile + ": " + strerror(errno));
-        if (fmt == KQ_TABLE_KWIG) out.direct(std::to_string(r.k) + "\n");
+        if (fmt == KQ_TABLE_KWIG) { const std::string head = std::to_string(r.k) + "\n"; text_bytes += head.size(); out.direct(gz ? bgzf_member(head.data(), head.size()) : head); }
         if (fmt == 0) { std::ostringstream index; write_bkwig_index(index, r, segs); out.direct(index.str()); }
         for (auto& s : r.seqs) { name_off.push_back((uint32_t)names.size()); names += s.header; }
         name_off.push_back((uint32_t)names.size());
     }
-    ~DeviceTableFile() { kq_dev_free(h, d_text); }
-    // a chunk that lies on the device -> the next page-locked buffer -> the file
+    ~DeviceTableFile() { kq_dev_free(h, d_text); kq_dev_free(h, d_gz); }
+    // a chunk that lies on the device -> the next page-locked buffer -> the file; as BGZF members when the name asks for them
     void copy_out(const void* d_src, uint64_t bytes) {
+        text_bytes += bytes;
+        if (gz) {
+            const uint64_t bound = kq_bgzf_bound(bytes, 0);
+            if (bound > d_gz_cap) {
+                kq_dev_free(h, d_gz); d_gz_cap = bound + bound / 8 + 4096; d_gz = (char*)kq_dev_alloc(h, d_gz_cap);
+                if (!d_gz) die("Error: no device memory for " + std::to_string(d_gz_cap) + " bytes of compressed table output");
+            }
+            const double t0 = now_s();
+            uint64_t n = 0;
+            kq_or_die(kq_deflate_bgzf_dev(h, (const char*)d_src, bytes, d_gz, d_gz_cap, &n, 0));
+            t_deflate += now_s() - t0;
+            d_src = d_gz; bytes = n;
+        }
         char* dst = out.next(bytes);
         const double t0 = now_s();
         kq_or_die(kq_copy_async(h, dst, d_src, bytes, KQ_COPY_TO_HOST));
@@ -189,7 +207,7 @@ struct DeviceTableFile {
             copy_out(d_text, need);
         }
     }
-    void finish() { out.wait(); }                                    // every chunk has reached the file
+    void finish() { if (gz) out.direct(bgzf_eof_marker()); out.wait(); }      // every chunk has reached the file
 };
 
 }  // namespace
@@ -214,6 +232,7 @@ bool table_device_wanted(const Run& r) { return env_flag("KQ_TABLE_DEVICE") && !
 // DeviceTableFile takes that payload to the file.  KQ_TABLE_TRACE=1 prints the wall clock of the steps to stderr.
 void write_per_base_device(Run& r) {
     verbose("per-base table written by the device formatter");
+    if (r.plan.table_gz) verbose("per-base table compressed by the device deflater");
     verbose("Validating sequence");
     kq_handle* h = r.h;
     const SegmentLists segs = all_segments(r.seqs);
@@ -247,7 +266,11 @@ void write_per_base_device(Run& r) {
     }
     file.finish();
     print_qv(r);
-    if (env_flag("KQ_TABLE_TRACE")) fprintf(stderr, "[table] device: lookup %.3f s, format %.3f s, copy %.3f s, write %.3f s, %llu bytes\n", t_lookup, file.t_format, file.t_copy, file.out.t_write, (unsigned long long)file.out.bytes);
+    if (env_flag("KQ_TABLE_TRACE")) {
+        fprintf(stderr, "[table] device: lookup %.3f s, format %.3f s, copy %.3f s, write %.3f s, %llu bytes", t_lookup, file.t_format, file.t_copy, file.out.t_write, (unsigned long long)(r.plan.table_gz ? file.text_bytes : file.out.bytes));
+        if (r.plan.table_gz) fprintf(stderr, ", deflate %.3f s, %llu compressed bytes", file.t_deflate, (unsigned long long)file.out.bytes);
+        fprintf(stderr, "\n");
+    }
 }
 
 // ---- the same under map-range passes: the triples accumulate on the device ------------------------------------------------
@@ -293,6 +316,7 @@ void table_passes_range(Run& r, TablePasses& t, int lo, int hi) {
 
 void table_passes_write(Run& r, TablePasses& t) {
     verbose("per-base table written by the device formatter");
+    if (r.plan.table_gz) verbose("per-base table compressed by the device deflater");
     verbose("per-base table accumulated on the device over " + std::to_string(t.n_ranges) + " map ranges in " + std::to_string(t.plan.groups.size()) + " calls");
     kq_handle* h = r.h;
     uint64_t ctr[3] = {0, 0, 0};
@@ -301,26 +325,40 @@ void table_passes_write(Run& r, TablePasses& t) {
     for (int i = 0; i < 3; ++i) r.counters[i] += ctr[i];
     kq_dev_free(h, t.d_text); kq_dev_free(h, t.d_pb); kq_dev_free(h, t.d_ctr);       // (room for the formatter's text)
     t.d_text = nullptr; t.d_pb = nullptr; t.d_ctr = nullptr;
-    uint64_t bytes = 0;
-    double t_format = 0, t_copy = 0, t_write = 0;
+    uint64_t bytes = 0, gz_bytes = 0;
+    double t_format = 0, t_copy = 0, t_write = 0, t_deflate = 0;
     {
         DeviceTableFile file(r, t.segs);
         for (const TableGroup& g : t.plan.groups) file.write_call(g.lo, g.hi, t.d_acc + 3 * g.first_triple, g.n_triples);
         file.finish();
-        bytes = file.out.bytes; t_format = file.t_format; t_copy = file.t_copy; t_write = file.out.t_write;
+        bytes = r.plan.table_gz ? file.text_bytes : file.out.bytes; gz_bytes = file.out.bytes; t_format = file.t_format; t_copy = file.t_copy; t_write = file.out.t_write; t_deflate = file.t_deflate;
     }
     table_passes_free(r, t);
-    if (t.trace) fprintf(stderr, "[table] device passes: lookup %.3f s, merge %.3f s, format %.3f s, copy %.3f s, write %.3f s, %llu bytes, %d map ranges, %llu calls\n",
-                         t.t_lookup, t.t_merge, t_format, t_copy, t_write, (unsigned long long)bytes, t.n_ranges, (unsigned long long)t.plan.groups.size());
+    if (t.trace) {
+        fprintf(stderr, "[table] device passes: lookup %.3f s, merge %.3f s, format %.3f s, copy %.3f s, write %.3f s, %llu bytes, %d map ranges, %llu calls",
+                t.t_lookup, t.t_merge, t_format, t_copy, t_write, (unsigned long long)bytes, t.n_ranges, (unsigned long long)t.plan.groups.size());
+        if (r.plan.table_gz) fprintf(stderr, ", deflate %.3f s, %llu compressed bytes", t_deflate, (unsigned long long)gz_bytes);
+        fprintf(stderr, "\n");
+    }
 }
 
 void write_per_base_host(const Run& r) {
     verbose("per-base table written by the host writer");
     const double t0 = now_s();
     const SegmentLists segs = all_segments(r.seqs);
-    if (r.plan.ext == "kwig") write_kwig(r, segs);
-    else if (r.plan.ext == "bkwig") write_bkwig(r, segs);
-    else write_table(r, segs);
+    const std::string& format = r.plan.table_format();
+    if (format == "bkwig") write_bkwig(r, segs);
+    else {
+        std::ofstream file(r.ui.outFile, std::ios::trunc | std::ios::out | std::ios::binary);
+        if (r.plan.table_gz) {                                       // the same text, through zlib into BGZF members
+            verbose("per-base table compressed by the host (zlib)");
+            BgzfBuf gz(file);
+            std::ostream ofs(&gz);
+            if (format == "kwig") write_kwig(r, segs, ofs, &gz); else write_table(r, segs, ofs);
+            if (!gz.finish()) die("Error: cannot write " + r.ui.outFile);
+        } else if (format == "kwig") write_kwig(r, segs, file, nullptr);
+        else write_table(r, segs, file);
+    }
     if (env_flag("KQ_TABLE_TRACE")) fprintf(stderr, "[table] host: write %.3f s\n", now_s() - t0);
 }
 

@@ -19,6 +19,9 @@ struct Run {
 void print_qv(const Run& r);              // src/kreeq.cpp:78-106; prints nothing for a -o name without a dot
 
 // -o x.kwig / .bkwig / .bed / .csvtable, by whichever side may write them; every byte is the same.
+// -o x.kwig.gz / .bed.gz / .csvtable.gz (OutPlan::table_gz): the same text as a BGZF file -- on the device paths every formatted
+// chunk is deflated there (kq_deflate_bgzf_dev), on the host path the writer's text goes through zlib (bgzf_out.h); the inflated
+// bytes are the plain format's on every path, the compressed bytes differ between the two sides.
 // Host: r.per_base was filled by the lookups of the map-range loop.
 // Device (KQ_TABLE_DEVICE=1, off by default; a resident table and no sequence above kDeviceCallBytes): nothing has been looked
 // up yet; the lookup keeps its per-base array on the GPU, which orients and formats it, and the QV table is printed at the end.

@@ -113,11 +113,11 @@ void run_ranges(Run& r, const std::vector<DbSource>& dbs, uint64_t read_bytes, i
     const UserInput& ui = r.ui;
     const OutPlan& plan = r.plan;
     const bool validate = ui.mode == 0, search = validate && plan.vcf && !ui.inSequence.empty();
-    const bool device_tables = validate && plan.per_base && n == 1 && table_device_wanted(r);
+    const bool device_tables = validate && plan.tables() && n == 1 && table_device_wanted(r);
     TablePasses acc;                                                 // (taken before the first fill: the count path sizes its arena around it)
-    const bool acc_tables = validate && plan.per_base && n > 1 && table_passes_wanted(r) && table_passes_begin(r, acc);
+    const bool acc_tables = validate && plan.tables() && n > 1 && table_passes_wanted(r) && table_passes_begin(r, acc);
     const bool lookup = validate && !ui.inSequence.empty() && !plan.vcf && !device_tables && !acc_tables;      // every other extension validates (src/kreeq-output.cpp:62-72)
-    if (lookup && plan.per_base) r.per_base.assign(r.genome.text.size(), kq_dbgbase{});
+    if (lookup && plan.tables()) r.per_base.assign(r.genome.text.size(), kq_dbgbase{});
     // where the ranges go when a later step needs them again: the .kreeq output, or a temporary database for the variant search
     std::string range_db;
     if (plan.kreeq) range_db = ui.outFile;
@@ -139,7 +139,7 @@ void run_ranges(Run& r, const std::vector<DbSource>& dbs, uint64_t read_bytes, i
         if (lookup) {
             verbose("Validating sequence");
             kq_or_die(kq_lookup_sequence(r.h, r.genome.text.data(), r.genome.text.size(), ui.covCutOff, (uint16_t)lo, (uint16_t)hi,
-                                         plan.per_base ? r.per_base.data() : nullptr, r.counters));
+                                         plan.tables() ? r.per_base.data() : nullptr, r.counters));
         }
         if (acc_tables) {
             verbose("Validating sequence");
@@ -163,7 +163,7 @@ void run_ranges(Run& r, const std::vector<DbSource>& dbs, uint64_t read_bytes, i
     if (device_tables) write_per_base_device(r);
     if (acc_tables) { table_passes_write(r, acc); print_qv(r); }
     if (lookup) print_qv(r);
-    if (validate && plan.per_base && !device_tables && !acc_tables) write_per_base_host(r);
+    if (validate && plan.tables() && !device_tables && !acc_tables) write_per_base_host(r);
     if (plan.hist) { std::ofstream ofs(ui.outFile); for (auto& kv : hist) ofs << kv.first << "\t" << kv.second << "\n"; }
     if (search) {
         if (n == 1) write_vcf(r, graph_of_handle(r.h));
