@@ -2,52 +2,18 @@
 // tests/test_deflate_core_host.py.  Every array the core touches is a heap block of exactly the size it may use: the Work record
 // (sizeof(Work), filled with garbage first) and the member (its final size).  Two tokenisers live here, not in the core: all
 // literals, and a greedy matcher with a one-entry hash table; a third source of tokens is a hand-made list whose expansion IS the
-// text (every length and distance symbol).  Every member is inflated in-process by kq_inflate_core.h and written to
-// <dir>/<name>.gz next to <dir>/<name>.txt for the pytest side (zlib, wbits = 31).
+// text (every length and distance symbol).  Every member is built and checked by make_member (deflate_member.h, shared with
+// deflate_tokens_main.cpp): inflated in-process by kq_inflate_core.h and written to <dir>/<name>.gz next to <dir>/<name>.txt
+// for the pytest side (zlib, wbits = 31).
 // Output: one line per member "member <name> <size> <dynamic> <max code length> <n_text>", lines "set ..." for the direct code
 // length cases, then "<failures> failures".
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
+#include "deflate_member.h"
 
-#include "kq_deflate_core.h"
-#include "kq_inflate_core.h"
-
-static int failures = 0;
-#define CHECK(cond, ...) do { if (!(cond)) { ++failures; printf("FAIL %s:%d %s: ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } while (0)
-
-struct Token { uint16_t len; uint16_t dist; uint8_t lit; };      // len 0: a literal; dist is stored minus one
-
-struct HeapMem {                                                  // the inflater's memory, as in inflate_core_main.cpp
-    std::unique_ptr<uint8_t[]> in, out;
-    std::unique_ptr<kqinf::Tables> tab;
-    HeapMem(const uint8_t* data, uint32_t data_len, uint32_t isize) : in(new uint8_t[data_len]), out(new uint8_t[isize]), tab(new kqinf::Tables) {
-        if (data_len) memcpy(in.get(), data, data_len);
-        memset(tab.get(), 0xA5, sizeof(kqinf::Tables));
-    }
-    uint32_t in_byte(uint32_t i) { return in[i]; }
-    void out_put(uint32_t pos, uint32_t b) { out[pos] = (uint8_t)b; }
-    void out_copy(uint32_t pos, uint32_t dist, uint32_t len) { for (uint32_t j = 0; j < len; ++j) out[pos + j] = out[pos - dist + j]; }
-    kqinf::Tables* tables() { return tab.get(); }
-    void st16(uint16_t* p, uint32_t v) { *p = (uint16_t)v; }
-    void st8(uint8_t* p, uint32_t v) { *p = (uint8_t)v; }
-    void tables_ready() {}
-};
-
-struct HeapSink {
-    std::unique_ptr<uint8_t[]> p;
-    uint32_t size;
-    explicit HeapSink(uint32_t n) : p(new uint8_t[n]), size(n) { memset(p.get(), 0xA5, n); }
-    bool put(uint32_t pos, uint32_t b) { if (pos >= size) return false; p[pos] = (uint8_t)b; return true; }
-};
-
-static uint32_t crc_of(const uint8_t* p, uint32_t n) {
-    uint32_t reg = 0xFFFFFFFFu;
-    for (uint32_t i = 0; i < n; ++i) reg = kqinf::crc_byte(reg, p[i]);
-    return ~reg;
+// make_member of deflate_member.h, reported
+static Made make_and_report(const std::string& dir, const std::string& name, const std::vector<uint8_t>& text, const std::vector<Token>& tok) {
+    const Made m = make_member(dir, name, text, tok);
+    if (m.size) printf("member %s %u %d %d %u\n", name.c_str(), m.size, m.dynamic ? 1 : 0, m.max_len, (uint32_t)text.size());
+    return m;
 }
 
 static std::vector<Token> all_literals(const std::vector<uint8_t>& t) {
@@ -85,70 +51,6 @@ static std::vector<uint8_t> expand(const std::vector<Token>& tok) {
         for (uint32_t j = 0; j < k.len; ++j) t.push_back(t[t.size() - (k.dist + 1u)]);
     }
     return t;
-}
-
-static uint32_t n_codes(const uint8_t* lens, int n) { uint32_t c = 0; for (int s = 0; s < n; ++s) c += lens[s] != 0; return c; }
-
-struct Made { uint32_t size = 0; bool dynamic = false; int max_len = 0; };
-
-// tokens (whose expansion is `text`) -> one member, checked and written out
-static Made make_member(const std::string& dir, const std::string& name, const std::vector<uint8_t>& text, const std::vector<Token>& tok) {
-    Made made;
-    const uint32_t n = (uint32_t)text.size();
-    std::unique_ptr<kqdef::Work> w(new kqdef::Work);
-    memset((void*)w.get(), 0xA5, sizeof(kqdef::Work));
-    kqdef::clear_freq(*w);
-    for (const Token& k : tok) { if (k.len) kqdef::count_match(*w, k.len, k.dist + 1u); else kqdef::count_literal(*w, k.lit); }
-    const kqdef::Plan plan = kqdef::plan_block(*w, n);
-    CHECK(plan.err == kqdef::OK, "%s: plan error %d", name.c_str(), plan.err);
-    if (plan.err) return made;
-    CHECK(plan.payload <= kqdef::STORED_BYTES + n, "%s: payload %u above the stored form", name.c_str(), plan.payload);
-    // the sets of the header, whether the block is taken or not
-    const uint32_t full = 1u << kqdef::MAX_BITS;
-    const uint32_t kl = kqdef::kraft_sum(w->llen, kqdef::N_LIT), kd = kqdef::kraft_sum(w->dlen, kqdef::N_DIST), kc = kqdef::kraft_sum(w->clen, kqdef::N_CLEN);
-    CHECK(kl == full, "%s: literal set sums to %u / 32768", name.c_str(), kl);
-    CHECK(kc == full, "%s: code-length set sums to %u / 32768", name.c_str(), kc);
-    CHECK(kd == full || (n_codes(w->dlen, kqdef::N_DIST) == 1 && kd == full / 2), "%s: distance set sums to %u / 32768", name.c_str(), kd);
-    for (int s = 0; s < kqdef::N_LIT; ++s) { CHECK(w->llen[s] <= kqdef::MAX_BITS, "llen"); if (w->llen[s] > made.max_len) made.max_len = w->llen[s]; }
-    for (int s = 0; s < kqdef::N_DIST; ++s) CHECK(w->dlen[s] <= kqdef::MAX_BITS, "dlen");
-    for (int s = 0; s < kqdef::N_CLEN; ++s) CHECK(w->clen[s] <= kqdef::MAX_CLEN_BITS, "%s: code-length code of %u bits", name.c_str(), w->clen[s]);
-    made.dynamic = plan.dynamic;
-    made.size = kqdef::HEADER_BYTES + plan.payload + kqdef::TRAILER_BYTES;
-    HeapSink sink(made.size);
-    for (uint32_t i = 0; i < kqdef::HEADER_BYTES; ++i) sink.put(i, kqdef::header_byte(i, made.size));
-    if (plan.dynamic) {
-        kqdef::BitWriter<HeapSink> bw(sink, kqdef::HEADER_BYTES);
-        for (uint32_t i = 0; i < w->n_items; ++i) bw.put(w->u.items[i] & 0xFFFFFFu, w->u.items[i] >> 24);
-        uint64_t bits; uint32_t nb;
-        for (const Token& k : tok) {
-            if (k.len) kqdef::match_bits(*w, k.len, k.dist + 1u, bits, nb); else kqdef::literal_bits(*w, k.lit, bits, nb);
-            CHECK(nb >= 1 && nb <= 48, "%s: a token of %u bits", name.c_str(), nb);
-            bw.put(bits, nb);
-        }
-        kqdef::literal_bits(*w, kqdef::EOB, bits, nb);
-        bw.put(bits, nb);
-        bw.finish();
-        CHECK(bw.err == kqdef::OK && bw.pos == kqdef::HEADER_BYTES + plan.payload, "%s: the writer ended at %u, planned %u", name.c_str(), bw.pos, kqdef::HEADER_BYTES + plan.payload);
-    } else {
-        for (uint32_t i = 0; i < kqdef::STORED_BYTES; ++i) sink.put(kqdef::HEADER_BYTES + i, kqdef::stored_byte(i, n));
-        for (uint32_t i = 0; i < n; ++i) sink.put(kqdef::HEADER_BYTES + kqdef::STORED_BYTES + i, text[i]);
-    }
-    const uint32_t crc = crc_of(text.data(), n);
-    for (uint32_t i = 0; i < kqdef::TRAILER_BYTES; ++i) CHECK(sink.put(kqdef::HEADER_BYTES + plan.payload + i, kqdef::trailer_byte(i, crc, n)), "trailer");
-    // the project's own inflater reads it back
-    HeapMem m(sink.p.get() + kqdef::HEADER_BYTES, plan.payload, n);
-    kqinf::Inflate<HeapMem> inf(m, plan.payload, n);
-    const int code = inf.run();
-    CHECK(code == kqinf::OK, "%s: inflate says %s", name.c_str(), kqinf::err_name(code));
-    CHECK(code != kqinf::OK || n == 0 || memcmp(m.out.get(), text.data(), n) == 0, "%s: the text differs", name.c_str());
-    FILE* f = fopen((dir + "/" + name + ".gz").c_str(), "wb");
-    FILE* g = fopen((dir + "/" + name + ".txt").c_str(), "wb");
-    if (!f || !g) { printf("cannot write into %s\n", dir.c_str()); ++failures; if (f) fclose(f); if (g) fclose(g); return made; }
-    fwrite(sink.p.get(), 1, made.size, f);
-    if (n) fwrite(text.data(), 1, n, g);
-    fclose(f); fclose(g);
-    printf("member %s %u %d %d %u\n", name.c_str(), made.size, plan.dynamic ? 1 : 0, made.max_len, n);
-    return made;
 }
 
 static uint32_t g_rng = 12345;
@@ -221,22 +123,22 @@ int main(int argc, char** argv) {
     // ---- whole members ----
     for (uint32_t n : {0u, 1u, 2u, 3u, 258u, 259u, 65280u}) {
         const std::vector<uint8_t> t = table_text(n);
-        make_member(dir, "table_" + std::to_string(n) + "_literals", t, all_literals(t));
-        const Made m = make_member(dir, "table_" + std::to_string(n) + "_greedy", t, greedy(t));
+        make_and_report(dir, "table_" + std::to_string(n) + "_literals", t, all_literals(t));
+        const Made m = make_and_report(dir, "table_" + std::to_string(n) + "_greedy", t, greedy(t));
         if (n == 65280) CHECK(m.dynamic && m.size < n / 2, "the table text compresses to %u bytes", m.size);
     }
     { std::vector<uint8_t> t(26); for (int i = 0; i < 26; ++i) t[(size_t)i] = (uint8_t)('a' + i); std::vector<uint8_t> tt; for (int r = 0; r < 40; ++r) { for (auto& b : t) b = (uint8_t)('a' + rnd() % 26); tt.insert(tt.end(), t.begin(), t.end()); }
-      const Made m = make_member(dir, "no_match", tt, all_literals(tt)); CHECK(m.dynamic, "no_match is dynamic"); }
-    { const std::vector<uint8_t> t(1000, 'A'); const Made m = make_member(dir, "one_distance_symbol", t, greedy(t)); CHECK(m.dynamic && m.size < 60, "A x 1000 takes %u bytes", m.size); }
-    { const std::vector<uint8_t> t(200, 'A'); const Made m = make_member(dir, "one_literal", t, all_literals(t)); CHECK(m.dynamic && m.max_len == 1, "one literal: longest code %d", m.max_len); }
-    { const std::vector<uint8_t> t(65280, 'A'); const Made m = make_member(dir, "A_65280", t, greedy(t)); CHECK(m.dynamic && m.size < 1024, "A x 65280 takes %u bytes", m.size); }
+      const Made m = make_and_report(dir, "no_match", tt, all_literals(tt)); CHECK(m.dynamic, "no_match is dynamic"); }
+    { const std::vector<uint8_t> t(1000, 'A'); const Made m = make_and_report(dir, "one_distance_symbol", t, greedy(t)); CHECK(m.dynamic && m.size < 60, "A x 1000 takes %u bytes", m.size); }
+    { const std::vector<uint8_t> t(200, 'A'); const Made m = make_and_report(dir, "one_literal", t, all_literals(t)); CHECK(m.dynamic && m.max_len == 1, "one literal: longest code %d", m.max_len); }
+    { const std::vector<uint8_t> t(65280, 'A'); const Made m = make_and_report(dir, "A_65280", t, greedy(t)); CHECK(m.dynamic && m.size < 1024, "A x 65280 takes %u bytes", m.size); }
     {   // literal frequencies 1, 2, 4, 7, 12 ... (each the sum of the two before it, plus one: no ties, so the tree is a chain) over 20
         // byte values: an unlimited code would be 20 bits deep
         std::vector<uint8_t> t;
         uint32_t a = 1, b = 2;
         for (int i = 0; i < 20; ++i) { t.insert(t.end(), a, (uint8_t)(40 + i)); const uint32_t c = a + b + 1; a = b; b = c; }
         for (size_t i = t.size(); i > 1; --i) std::swap(t[i - 1], t[rnd() % i]);
-        const Made m = make_member(dir, "fibonacci_text", t, all_literals(t));
+        const Made m = make_and_report(dir, "fibonacci_text", t, all_literals(t));
         CHECK(m.dynamic && m.max_len == 15, "fibonacci text: longest code %d", m.max_len);
     }
     {   // all 286 literal / length codes and all 30 distance codes: the token list is made by hand, the text is its expansion
@@ -259,13 +161,13 @@ int main(int argc, char** argv) {
         w->lfreq[256] = 1;
         for (int s = 0; s < kqdef::N_LIT; ++s) CHECK(w->lfreq[s] > 0, "all symbols: literal / length code %d unused", s);
         for (int s = 0; s < kqdef::N_DIST; ++s) CHECK(w->dfreq[s] > 0, "all symbols: distance code %d unused", s);
-        make_member(dir, "all_symbols", t, tok);
+        make_and_report(dir, "all_symbols", t, tok);
     }
     for (uint32_t n : {1000u, 65280u}) {                            // random bytes: the stored block, at exactly 18 + 5 + n + 8
         std::vector<uint8_t> t(n);
         for (auto& b : t) b = (uint8_t)rnd();
-        const Made a = make_member(dir, "random_" + std::to_string(n) + "_literals", t, all_literals(t));
-        const Made g = make_member(dir, "random_" + std::to_string(n) + "_greedy", t, greedy(t));
+        const Made a = make_and_report(dir, "random_" + std::to_string(n) + "_literals", t, all_literals(t));
+        const Made g = make_and_report(dir, "random_" + std::to_string(n) + "_greedy", t, greedy(t));
         CHECK(!a.dynamic && a.size == 18 + 5 + n + 8, "random bytes, literals: %u bytes", a.size);
         CHECK(!g.dynamic && g.size == 18 + 5 + n + 8, "random bytes, greedy: %u bytes", g.size);
     }

@@ -3,7 +3,8 @@ the output back, the project's block walk accepts every member, the device infla
 the alignment of the text or on the call, and the sizes meet conditions that are derived, not tuned: no member above its stored
 form, 65 280 x 'A' below 1 KiB (253 matches of 258 bytes cost 13 bits each even with fixed codes, about 411 bytes: only
 maximal-length matches get there), and every full member of a formatted table below its order-0 entropy bound, which Huffman
-coding without matches cannot reach.  The CPU tests of the code builder (tests/test_deflate_core_host.py) come first."""
+coding without matches cannot reach.  The CPU tests of the code builder (tests/test_deflate_core_host.py) come first; WHICH
+tokens and bytes the device writes is held to a restatement of its parse in tests/test_gpu_deflate_parse.py."""
 import gzip
 import zlib
 
@@ -113,19 +114,23 @@ def check_container(data, text, eof):
     return blocks
 
 
-def deflate_dev(db, text, offset=0, flags=0):
-    """kq_deflate_bgzf_dev with the text `offset` bytes behind a 16-byte boundary and the output 3 bytes behind one, guarded"""
+def deflate_dev(db, text, offset=0, flags=0, out_offset=3, src=None):
+    """kq_deflate_bgzf_dev with the text `offset` bytes behind a 16-byte boundary (or in `src`, a device tensor that holds it
+    already) and the output `out_offset` bytes behind one, guarded"""
     import torch
     from kreeq_amd import capi
 
-    src = on_device(text, offset)
+    if src is None:
+        src = on_device(text, offset)
     cap = capi.bgzf_bound(len(text), flags)
-    out = torch.full((16 + 3 + cap + 48,), GUARD, dtype=torch.uint8, device="cuda")
+    lead = 16 + out_offset
+    out = torch.full((lead + cap + 48,), GUARD, dtype=torch.uint8, device="cuda")
+    assert out.data_ptr() % 16 == 0
     torch.cuda.synchronize()
-    n = db.deflate_bgzf_dev(src.data_ptr() if len(text) else 0, len(text), out.data_ptr() + 19, cap, flags)
+    n = db.deflate_bgzf_dev(src.data_ptr() if len(text) else 0, len(text), out.data_ptr() + lead, cap, flags)
     got = out.cpu().numpy()
-    assert (got[:19] == GUARD).all() and (got[19 + n:] == GUARD).all(), "bytes outside the output were written"
-    return got[19:19 + n].tobytes()
+    assert (got[:lead] == GUARD).all() and (got[lead + n:] == GUARD).all(), "bytes outside the output were written"
+    return got[lead:lead + n].tobytes()
 
 
 def inflate_dev(db, data):
