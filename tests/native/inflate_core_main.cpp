@@ -6,7 +6,7 @@
 //   expect 0        the member must decode to exactly the text
 //   expect 1..13    the member must end in that error code (13 = CRC-32 mismatch, found here as in the kernel: after the decode)
 //   expect 255      either: the text exactly, or any error code
-// Output: one line per case "case i code max_len max_dist", then "<failures> failures".
+// Output: per case one line "case i code max_len max_dist" and one line "name i <err_name(code)>", then "<failures> failures".
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -87,6 +87,7 @@ int main(int argc, char** argv) {
         else ok = code == (int)expect;
         if (!ok) { printf("case %u: expected %u, got %d (%s)\n", c, expect, code, kqinf::err_name(code)); ++failures; }
         printf("case %u %d %d %u\n", c, code, inf.max_len, m.max_dist);
+        printf("name %u %s\n", c, kqinf::err_name(code));
     }
     fclose(f);
     printf("%d failures\n", failures);

@@ -12,6 +12,7 @@ import pytest
 
 from tests import bgzf_inputs as B
 from tests import helpers as H
+from tests import inflate_streams as S
 
 CSRC = os.path.join(H.ROOT, "kreeq_amd", "csrc")
 
@@ -81,34 +82,7 @@ def test_mutations_give_their_error_codes(exe, tmp_path, good):
 def test_more_invalid_streams(exe, tmp_path):
     """the rest of the core's error list: repeat with nothing before it, an incomplete literal set, symbol 286, distance code 30,
     trailing bytes, a missing end-of-block code when the input ends"""
-    W = B.BitWriter
-
-    def dyn(clens, body):
-        """dynamic header with HCLEN 19 and the code-length code lengths `clens` (indexed by symbol), then body(w)"""
-        w = W().bits(1, 1).bits(2, 2).bits(0, 5).bits(0, 5).bits(15, 4)
-        for s in (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15):
-            w.bits(clens.get(s, 0), 3)
-        body(w)
-        return w.bits(0, 24).done()
-
-    cases = []
-    # code-length code {16: 1 bit, 0: 1 bit}: canonical codes 0 -> symbol 0, 1 -> symbol 16; the first symbol is 16
-    cases.append((B.ERR_REPEAT, dyn({16: 1, 0: 1}, lambda w: w.code(1, 1).bits(0, 2))))
-    # code-length code {1: 1 bit, 18: 1 bit}: 0 -> symbol 1, 1 -> symbol 18.  257 literal lengths of 1 bit: over-subscribed
-    cases.append((B.ERR_OVERSUBSCRIBED, dyn({1: 1, 18: 1}, lambda w: [w.code(0, 1) for _ in range(258)])))
-    # {2: 1 bit, 18: 1 bit}: 0 -> symbol 2, 1 -> symbol 18: literal 0 and end-of-block 2 bits each, nothing else: incomplete
-    def incomplete(w):
-        w.code(0, 1)                                               # literal 0: 2 bits
-        w.code(1, 1).bits(138 - 11, 7).code(1, 1).bits(117 - 11, 7)      # 255 zeros
-        w.code(0, 1)                                               # 256: 2 bits
-        w.code(0, 1)                                               # the one distance length
-    cases.append((B.ERR_INCOMPLETE, dyn({2: 1, 18: 1}, incomplete)))
-    cases.append((B.ERR_SYMBOL, W().bits(1, 1).bits(1, 2).fixed_lit(286).bits(0, 16).done()))
-    cases.append((B.ERR_DIST_CODE, W().bits(1, 1).bits(1, 2).fixed_lit(ord("a")).fixed_lit(257).code(30, 5).bits(0, 16).done()))
-    cases.append((B.ERR_TRAILING, W().bits(1, 1).bits(1, 2).fixed_lit(ord("a")).fixed_lit(256).done() + b"\0"))
-    cases.append((B.ERR_INPUT_END, W().bits(1, 1).bits(1, 2).fixed_lit(ord("a")).done()))
-    cases.append((B.ERR_INPUT_END, W().bits(0, 1).bits(1, 2).fixed_lit(ord("a")).fixed_lit(256).done()))      # not the final block, and no other follows
-    cases.append((B.ERR_INPUT_END, b""))
+    cases = S.more_invalid_streams()                               # (the list lives with the other streams: the kernel runs it too)
     got = run_cases(exe, tmp_path, [(code, B.member(raw, zlib.crc32(b"a"), 1), b"") for code, raw in cases])
     assert [g[0] for g in got] == [code for code, _ in cases]
     # zlib does not take any of them for a whole stream either
