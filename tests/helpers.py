@@ -119,6 +119,16 @@ def entries_equal(a, b):
     return all(np.array_equal(a[f], b[f]) for f in ("key", "fw", "bw", "cov", "hc"))
 
 
+def host_map_files(tmp, entries, map_count, lo, hi):
+    """-> ([bytes of .map.<m>.bin for m in lo..hi-1] as the HOST writer makes them, its high-copy entries)"""
+    from kreeq_amd import hostdb
+
+    ent = entries[(entries["key"] % np.uint64(map_count) >= lo) & (entries["key"] % np.uint64(map_count) < hi)]
+    d = os.path.join(str(tmp), f"host_{lo}_{hi}_{len(os.listdir(str(tmp)))}")
+    hc = hostdb.write_maps(d, map_count, lo, hi, ent)
+    return [open(os.path.join(d, f".map.{m}.bin"), "rb").read() for m in range(lo, hi)], hc
+
+
 def synth_reads(n_reads, read_len, genome_len, seed, err=0.005, n_rate=0.0, sep=b"\n"):
     """small deterministic synthetic read batch for parity tests (numpy PCG64)."""
     rng = np.random.default_rng(seed)

@@ -36,12 +36,7 @@ def np_submap(keys):
     return ((h >> np.uint64(8)) ^ (h >> np.uint64(16)) ^ (h >> np.uint64(24))) & np.uint64(255)
 
 
-def host_files(tmp, entries, map_count, lo, hi):
-    """-> ([bytes of .map.<m>.bin for m in lo..hi-1] as the HOST writer makes them, its high-copy entries)"""
-    ent = entries[(entries["key"] % np.uint64(map_count) >= lo) & (entries["key"] % np.uint64(map_count) < hi)]
-    d = os.path.join(str(tmp), f"host_{lo}_{hi}_{len(os.listdir(str(tmp)))}")
-    hc = hostdb.write_maps(d, map_count, lo, hi, ent)
-    return [open(os.path.join(d, f".map.{m}.bin"), "rb").read() for m in range(lo, hi)], hc
+host_files = H.host_map_files
 
 
 def check_range(db, tmp, lo, hi, entries=None):

@@ -28,13 +28,7 @@ def counted(kq, k, reads, hint=1 << 16):
     return db
 
 
-def want_of(g, text, depth, span):
-    """the oracle over the segments of `text` -> [(pos, seg_start, type, refLen, sequence)] in the ABI's coordinates"""
-    text = text.decode() if isinstance(text, bytes) else text
-    out = []
-    for start, seg in V.segments_of(text):
-        out += [(start + pos, start, t, r, s) for _, pos, t, r, s in C.expected(g, [seg], depth, span)]
-    return out
+want_of = C.want_of
 
 
 def check(db, g, text, depth, span, cutoff=0):

@@ -43,6 +43,15 @@ def expected(g, segments, depth, span):
     return out
 
 
+def want_of(g, text, depth, span):
+    """the oracle over the segments of `text` -> [(pos, seg_start, type, refLen, sequence)] in the ABI's coordinates"""
+    text = text.decode() if isinstance(text, bytes) else text
+    out = []
+    for start, seg in V.segments_of(text):
+        out += [(start + pos, start, t, r, s) for _, pos, t, r, s in expected(g, [seg], depth, span)]
+    return out
+
+
 def window_stats(k, segment, span):
     """the targets of every position of a segment, by the reference's own queue / map steps (oracle/variants.py:326-341) ->
     (positions whose queue holds a key twice, positions where a queued key is missing from the map: the erase quirk)"""
