@@ -172,7 +172,10 @@ void* kq_get_stream(kq_handle* h);
  *                          bytes of one search's state block at the call's depth and span.  Results never depend on it. */
 enum { KQ_OPT_TRUST_CAPACITY = 1, KQ_OPT_COUNT_PATH = 2, KQ_OPT_SLICE_KMERS = 3, KQ_OPT_COUNT_MAP_RANGE = 4, KQ_OPT_PROFILE = 5,
        KQ_OPT_LOOKUP_PATH = 6, KQ_OPT_MERGE_PATH = 7, KQ_OPT_NARROW_MID = 8, KQ_OPT_PENDING_BYTES = 9, KQ_OPT_BUCKET_WINDOW = 10, KQ_OPT_OVERLAP = 11, KQ_OPT_COUNT_MAP_PASSES = 12, KQ_OPT_KERNEL_SET = 13, KQ_OPT_SHARD_WINDOW = 14, KQ_OPT_SUBGRAPH_BATCH = 15, KQ_OPT_VARIANT_BATCH = 16,
-       KQ_OPT_TEST_FAIL_PLAN = 100 /* failure-path tests only: the next partition plan of a count fails with KQ_ERR_NOMEM */ };
+       KQ_OPT_TEST_FAIL_PLAN = 100 /* failure-path tests only: the next partition plan of a count fails with KQ_ERR_NOMEM */,
+       KQ_OPT_TEST_EXPORT = 101 /* export-path tests only (results never depend on it; default 0): bit 0 = key order on the host, as when the device
+                                   has no memory for the sort (kq_export; kq_export_map_images and kq_subgraph_gfa have no host sort and fail
+                                   with KQ_ERR_NOMEM), bit 1 = results leave the device through the bounce buffers at any size, 4096 bytes a chunk */ };
 int  kq_set_option(kq_handle* h, int option, int64_t value);
 int  kq_get_profile(kq_handle* h, char* buf, uint64_t cap);
 int  kq_sync(kq_handle* h);

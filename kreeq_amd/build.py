@@ -15,7 +15,7 @@ CLI = os.path.join(PKG, "bin", "kreeq")
 HOSTLIB = os.path.join(PKG, "lib", "libkreeq_host.so")       # .kreeq database files for the multi-GPU driver (no GPU code)
 
 HIP_SOURCES = [os.path.join(PKG, "csrc", "kreeq_amd.hip")]
-HIP_DEPS = HIP_SOURCES + [os.path.join(PKG, "csrc", f) for f in ("kq_device.h", "kq_partition.h", "kq_kernels.h", "kq_fastx.h", "kq_bgzf.h", "kq_bgzf_host.h", "kq_inflate_core.h", "kq_deflate.h", "kq_deflate_core.h", "kq_dbimage.h", "kq_dbimage_host.h", "kq_mem_host.h", "kq_plan_host.h", "kq_roff_host.h", "kq_seg_gate_host.h", "kq_select_host.h", "kq_formats.h", "kq_subgraph.h", "kq_gfa.h", "kq_bestfirst_core.h", "kq_nodequeue_core.h", "kq_variant_core.h", "kq_variants.h", "kq_table_core.h", "kq_table.h")] + [os.path.join(ROOT, "include", "kreeq_amd.h")]
+HIP_DEPS = HIP_SOURCES + [os.path.join(PKG, "csrc", f) for f in ("kq_device.h", "kq_partition.h", "kq_kernels.h", "kq_fastx.h", "kq_bgzf.h", "kq_bgzf_host.h", "kq_inflate_core.h", "kq_deflate.h", "kq_deflate_core.h", "kq_dbimage.h", "kq_dbimage_host.h", "kq_mem_host.h", "kq_export_host.h", "kq_plan_host.h", "kq_roff_host.h", "kq_seg_gate_host.h", "kq_select_host.h", "kq_formats.h", "kq_subgraph.h", "kq_gfa.h", "kq_bestfirst_core.h", "kq_nodequeue_core.h", "kq_variant_core.h", "kq_variants.h", "kq_table_core.h", "kq_table.h")] + [os.path.join(ROOT, "include", "kreeq_amd.h")]
 HOST_DIR = os.path.join(PKG, "host")
 DECOMPRESSOR_DIR = os.path.join(HOST_DIR, "decompressor")      # a directory of its own: host_sources() takes every host/*.cpp into the kreeq binary
 DECOMPRESSOR = os.path.join(PKG, "bin", "kreeq-decompressor")

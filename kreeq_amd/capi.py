@@ -261,7 +261,7 @@ class KreeqDB:
         """option: 'trust_capacity' | 'count_path' ('auto'|'direct'|'partitioned') | 'slice_kmers' | 'count_map_range' ((lo, hi)) |
         'kernel_set' (measurement only: mask of bits 1, 2, 4, 16, 32, 64, 128 -- KQ_OPT_KERNEL_SET in include/kreeq_amd.h; 32 / 64 = the last
         split level never / wherever possible with one workgroup per segment; 128 = the previous P1 scatter behind a map-range filter) | ..."""
-        opt = {"trust_capacity": 1, "count_path": 2, "slice_kmers": 3, "count_map_range": 4, "profile": 5, "lookup_path": 6, "merge_path": 7, "narrow_mid": 8, "pending_bytes": 9, "bucket_window": 10, "overlap": 11, "count_map_passes": 12, "kernel_set": 13, "shard_window": 14, "subgraph_batch": 15, "variant_batch": 16, "test_fail_plan": 100}[option]
+        opt = {"trust_capacity": 1, "count_path": 2, "slice_kmers": 3, "count_map_range": 4, "profile": 5, "lookup_path": 6, "merge_path": 7, "narrow_mid": 8, "pending_bytes": 9, "bucket_window": 10, "overlap": 11, "count_map_passes": 12, "kernel_set": 13, "shard_window": 14, "subgraph_batch": 15, "variant_batch": 16, "test_fail_plan": 100, "test_export": 101}[option]
         if option == "count_map_range":
             value = int(value[0]) | (int(value[1]) << 16)
         if option in ("count_path", "lookup_path", "merge_path"):

@@ -1977,7 +1977,7 @@ __global__ __launch_bounds__(256) void k_export(TableView t, uint32_t map_count,
             if (w0[j] == 0) continue;
             key[j] = key_of_hash(slot_hash(t, w0[j] & REM_MASK, (tile * 1024 + j * 256 + tid) >> REGION_SHIFT), t.k);
             const uint32_t m = (uint32_t)(key[j] % map_count);
-            if (m >= lo && m < hi) take |= 1u << j;
+            if (export_in_range(m, lo, hi)) take |= 1u << j;
         }
         const uint32_t mine = __popc(take);
         uint32_t incl = mine;
@@ -1995,7 +1995,7 @@ __global__ __launch_bounds__(256) void k_export(TableView t, uint32_t map_count,
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (!((take >> j) & 1u)) continue;
-                if (o < cap) {
+                if (export_has_place(o, cap)) {
                     const uint64_t idx = tile * 1024 + j * 256 + tid;
                     const Logical L = logical_of(t, slot_hash(t, w0[j] & REM_MASK, idx >> REGION_SHIFT), w0[j], e8[j]);
                     kq_entry e;

@@ -21,6 +21,7 @@
 #include "kq_device.h"
 #include "kq_partition.h"
 #include "kq_mem_host.h"
+#include "kq_export_host.h"
 #include "kq_plan_host.h"
 #include "kq_roff_host.h"
 #include "kq_seg_gate_host.h"
@@ -243,6 +244,7 @@ struct kq_handle {
     bool hist_cache_off = false;         // the batch being counted lives in a library-owned buffer, which keeps its address and
                                          // changes its content: the address-keyed KQ_OPT_COUNT_MAP_PASSES cache must not see it
     bool test_fail_plan = false;         // KQ_OPT_TEST_FAIL_PLAN: the next partition plan fails with KQ_ERR_NOMEM (failure-path tests)
+    int test_export = 0;                 // KQ_OPT_TEST_EXPORT: bit 0 = sort_entries_dev finds no memory, bit 1 = copy_out_bounced takes chunks of 4096 bytes at any size (tests)
     DevMem hot;                          // k_count_regions' list of skewed regions
     uint64_t var_batch = 0;              // KQ_OPT_VARIANT_BATCH: searches per batch of kq_search_variants, 0 = from the scratch budget
     uint64_t sg_batch = 0;               // KQ_OPT_SUBGRAPH_BATCH: searches per batch of kq_subgraph_best_first, 0 = from the scratch budget
@@ -626,6 +628,9 @@ int kq_set_option(kq_handle* h, int option, int64_t value) {
             h->lookup_path = (int)value; return KQ_OK;
         case KQ_OPT_PROFILE: h->profile = value != 0; if (!h->profile) marks_reset(h); return KQ_OK;
         case KQ_OPT_TEST_FAIL_PLAN: h->test_fail_plan = value != 0; return KQ_OK;
+        case KQ_OPT_TEST_EXPORT:
+            if (value < 0 || value > 3) return fail(KQ_ERR_INVALID, "KQ_OPT_TEST_EXPORT must be in [0, 3]");
+            h->test_export = (int)value; return KQ_OK;
         case KQ_OPT_COUNT_MAP_PASSES: {
             if (value != 1 && value != 2 && value != 4 && value != 8) return fail(KQ_ERR_INVALID, "KQ_OPT_COUNT_MAP_PASSES must be 1, 2, 4 or 8");
             if ((h->map_count & (h->map_count - 1)) != 0 || value > h->map_count) return fail(KQ_ERR_INVALID, "KQ_OPT_COUNT_MAP_PASSES needs a power-of-two map count");
@@ -2500,7 +2505,7 @@ int kq_import(kq_handle* h, const kq_entry* entries, uint64_t n) {
 static bool sort_entries_dev(kq_handle* h, DevScope& mem, const kq_entry* d_in, uint64_t n, kq_entry** d_sorted_out) {
     kq_entry* d_sorted = nullptr; uint64_t *d_k1 = nullptr, *d_k2 = nullptr; uint32_t *d_i1 = nullptr, *d_i2 = nullptr; void* d_tmp = nullptr;
     size_t tmp_bytes = 0;
-    bool on_device = n < (1ull << 32) &&
+    bool on_device = n < (1ull << 32) && !(h->test_export & 1) &&
         hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_k1, d_k2, d_i1, d_i2, (int64_t)n, 0, 2 * h->k, h->stream) == hipSuccess &&
         mem.alloc((void**)&d_sorted, n * sizeof(kq_entry)) == hipSuccess && mem.alloc((void**)&d_k1, n * 8) == hipSuccess &&
         mem.alloc((void**)&d_k2, n * 8) == hipSuccess && mem.alloc((void**)&d_i1, n * 4) == hipSuccess &&
@@ -2521,25 +2526,16 @@ static bool sort_entries_dev(kq_handle* h, DevScope& mem, const kq_entry* d_in, 
 // device -> caller: through two pinned bounce buffers (a copy into pageable memory runs at a fraction of the PCIe
 // rate: 0.25 s for 850 MB); the DMA of chunk i+1 overlaps the host copy of chunk i
 static hipError_t copy_out_bounced(kq_handle* h, void* out, const void* src, size_t bytes) {
-    const size_t chunk = (size_t)16 << 20;
+    const bool test_chunks = (h->test_export & 2) != 0;
+    const BouncePlan p = bounce_plan(bytes, test_chunks ? EXPORT_TEST_CHUNK : EXPORT_CHUNK, test_chunks);
     PinnedMem bounce[2];
-    hipError_t e;
-    if (bytes > 4 * chunk && bounce[0].alloc(chunk) == hipSuccess && bounce[1].alloc(chunk) == hipSuccess) {
-        const size_t n_chunks = (bytes + chunk - 1) / chunk;
-        auto len_of = [&](size_t c) { return std::min(chunk, bytes - c * chunk); };
-        e = hipMemcpyAsync(bounce[0].get(), (const char*)src, len_of(0), hipMemcpyDeviceToHost, h->stream);
-        for (size_t c = 0; c < n_chunks && e == hipSuccess; ++c) {
-            e = hipStreamSynchronize(h->stream);
-            if (e == hipSuccess && c + 1 < n_chunks)
-                e = hipMemcpyAsync(bounce[(c + 1) & 1].get(), (const char*)src + (c + 1) * chunk, len_of(c + 1), hipMemcpyDeviceToHost, h->stream);
-            memcpy((char*)out + c * chunk, bounce[c & 1].get(), len_of(c));
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    } else {
-        (void)hipGetLastError();
-        e = hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost);
-    }
-    return e;
+    if (p.bounced && bounce[0].alloc(p.chunk) == hipSuccess && bounce[1].alloc(p.chunk) == hipSuccess)
+        return bounce_copy(p, hipSuccess,
+            [&](int b, size_t off, size_t len) { return hipMemcpyAsync(bounce[b].get(), (const char*)src + off, len, hipMemcpyDeviceToHost, h->stream); },
+            [&]() { return hipStreamSynchronize(h->stream); },
+            [&](size_t off, int b, size_t len) { memcpy((char*)out + off, bounce[b].get(), len); });
+    (void)hipGetLastError();
+    return hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost);
 }
 
 int kq_export(kq_handle* h, uint16_t map_lo, uint16_t map_hi, kq_entry* out, uint64_t cap, uint64_t* n_out) {
